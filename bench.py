@@ -6,8 +6,20 @@ procedural heightfield hf1M, binned-SAH index BVH, 1920x1
 closest-hit ray per pixel + 8 cosine-hemisphere any-hit AO rays (radius 0.1) per hit pixel.
 A "step" is one frame.  Inputs (BVH, primitives, normals) are resident in HBM before timing.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does what the headline figure needs and nothing else: scene set-up, the W warm-up frames,
+the settle launches, the K timed frames, and one JSON line with the headline (`metric`, `value`, `unit`,
+`ms_per_step`, ...), the configuration and the settle record.  --full adds every other leg described
+below -- the CPU baseline, the counting pass and the roofline, the checks against the fixtures, the
+hip_sched::frame legs, the moving-camera leg and the user-kernel legs -- and their keys to the line.
+
+--dump-outputs DIR: after the timed frames rank 0 writes the last timed frame as the caller's render
+target holds it, one DIR/<name>.npy per buffer (color, prim_id, t, occ; float32, integers wider than
+two bytes as float64).  When the buffers pass DUMP_BYTES, all of them keep the same fixed, seeded
+sample of pixels, whose indices are DIR/pixels.npy.  The scene, the camera and the frame numbers depend
+on the arguments alone, so two runs with the same arguments write the same arrays.
 
 --gpus N > 1 without a launcher (no WORLD_SIZE): bench.py starts the N ranks itself as child processes
 before anything touches the GPU (launch_plan / spawn_ranks); with fewer GPUs than N, or WORLD_SIZE
@@ -15,8 +27,9 @@ disagreeing with --gpus, it exits 2 with a message and prints no line.
 
 Frames: every frame has its own frame number (vrh_render's frame_num -> its own AO sample set,
 as the reference reseeds per frame, cuda_sched.inl:38-45, 79): the W warm-up frames are numbers
-1..W, the K timed frames W+1..W+K; frame 0 and frame 3 are rendered once, untimed, and checked
-against the reference's fixtures (tests/golden).
+1..W, the K timed frames W+1..W+K (the untimed launches between them do not move the numbering);
+with --full, frame 0 and frame 3 are rendered once, untimed, and checked against the reference's
+fixtures (tests/golden).
 
 Frames in flight: the K timed frames run as K / F persistent launches of F frames each
 (vrh_render_batch; F = the largest divisor of K not above --frames-in-flight), so the kernel's
@@ -35,7 +48,7 @@ SURVEY.md §8e) of every frame and libvrh gathers the packed shards to rank 0 wi
 ncclRecv on its own stream and un-interleaves them there (vrh_render_sharded).  K frames are
 fixed as N grows: scaling "strong".
 
-Rank 0 prints one JSON line (the contract of the task statement) with:
+With --full, rank 0's JSON line also carries:
   * roofline: the unit that binds the traversal kernel is the vector-memory path (L1 / TA / TD:
     TD busy 94-97 % of the launch, PMC in profiles/r02_*), so `achieved` is the kernel's vector-L1
     request rate -- rocprofv3's TCP_TOTAL_CACHE_ACCESSES of the committed PMC pass of this exact
@@ -77,6 +90,11 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=64, help="timed frames")
     ap.add_argument("--warmup", type=int, default=32, help="untimed frames before the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline: CPU baseline, counting pass and roofline, checks "
+                         "against the fixtures, hip_sched::frame legs, moving-camera leg, user-kernel legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed frame's buffers as DIR/<name>.npy (rank 0)")
     ap.add_argument("--scene", default="hf1M", help="hf1M (C3, default) | hf10M (C4) | sph1M (C5)")
     ap.add_argument("--kernel", default=None, choices=["ao", "primary"], help="default: ao for triangles")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -308,6 +326,31 @@ def frames_per_launch(steps, cap):
     return max(d for d in range(1, cap + 1) if steps % d == 0)
 
 
+DUMP_BYTES = 62 * 10**6         # --dump-outputs: all arrays together, under 64 MB with their headers
+DUMP_SEED = 20240501            # the pixel sample of a frame that is larger
+
+
+def dump_outputs(dirname, buffers):
+    """Write one frame's buffers (name -> array with one row per pixel) as dirname/<name>.npy: float32,
+    integers wider than two bytes as float64 (every value exact).  Buffers above DUMP_BYTES keep the same
+    seeded sample of pixels, in image order, and pixels.npy holds their indices.  Returns what was written."""
+    import numpy as np
+    out = {k: np.ascontiguousarray(a, dtype=np.float64 if a.dtype.kind in "iu" and a.dtype.itemsize > 2 else np.float32)
+           for k, a in buffers.items()}
+    n = len(next(iter(out.values())))
+    per_pixel = sum(a.nbytes // n for a in out.values())
+    if per_pixel * n > DUMP_BYTES:
+        keep = DUMP_BYTES // (per_pixel + 8)
+        pix = np.sort(np.random.default_rng(DUMP_SEED).choice(n, keep, replace=False))
+        out = {k: a[pix] for k, a in out.items()}
+        out["pixels"] = pix.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
+    return {"dir": dirname, "pixels": int(len(next(iter(out.values())))), "of": int(n),
+            "arrays": {k: [str(a.dtype), list(a.shape)] for k, a in out.items()}}
+
+
 def load_json(path):
     try:
         with open(path) as f:
@@ -438,7 +481,7 @@ def main():
 
     # ---- CPU baseline (rank 0, N = 1 only), before any GPU work ------------------------------
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             cpu = cpu_baseline(args.scene, kernel, args.cpu_threads)
         except Exception as e:  # reported, never fatal for the GPU measurement
@@ -513,12 +556,14 @@ def main():
 
     # ---- counting pass (untimed, one frame on rank 0's whole image): tests and L1 lines per ray --
     rt_one = va.hip_buffer_rt(ctx, W, H)
-    va.render(ctx, dev, rt_one, basis, kern_count, None, frame_num=0)
-    cstats = ctx.last_frame_stats()
+    cstats = None
+    if args.full:
+        va.render(ctx, dev, rt_one, basis, kern_count, None, frame_num=0)
+        cstats = ctx.last_frame_stats()
 
     # ---- fixtures: frame 0 and frame 3 against the reference's outputs (untimed) ---------------
     verify = {}
-    if not args.no_verify and rank == 0:
+    if args.full and not args.no_verify and rank == 0:
         golden = load_json(os.path.join(ROOT, "tests", "golden", "golden.json")) or {}
         for case, fnum in ((args.scene, 0), (f"frame3_{args.scene}", 3)):
             g = golden.get(case)
@@ -556,7 +601,8 @@ def main():
               "frames_per_launch": F}
     ctx.stats_reset()
     barrier()
-    first_timed = next_frame[0]
+    # the timed frames are W+1..W+K however many settle launches the clock asked for
+    first_timed = next_frame[0] = args.warmup + 1
     t0 = time.perf_counter()
     for _ in range(launches):
         run_batch(F)
@@ -564,9 +610,16 @@ def main():
     elapsed = time.perf_counter() - t0
     acc = ctx.accum_stats()
 
+    # ---- --dump-outputs: the last timed frame (the last frame of the last launch) as rank 0's target
+    # holds it, before any later leg renders into that target
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        n = W * H
+        dumped = dump_outputs(args.dump_outputs, {k: a[(F - 1) * n:F * n] for k, a in target(F).download().items()})
+
     # ---- the timed frames are distinct and correct: the last launch's first and last frame equal
     # their own single-frame render (rank 0, untimed)
-    if not args.no_verify and rank == 0:
+    if args.full and not args.no_verify and rank == 0:
         last = target(F).download(t=False)
         n = W * H
         one = va.hip_buffer_rt(ctx, W, H)
@@ -586,7 +639,7 @@ def main():
 
     # ---- hip_sched::frame leg: one synchronous launch per frame (rank 0, N = 1) ---------------------
     single = None
-    if world == 1 and args.single_frames > 0:
+    if args.full and world == 1 and args.single_frames > 0:
         rt_s = va.hip_buffer_rt(ctx, W, H)
         sched = va.hip_sched(ctx, async_frames=False)       # frame() returns when the frame is done
         sp = va.make_sched_params(va.pixel_sampler.uniform_type, cam, rt_s)
@@ -611,7 +664,7 @@ def main():
     # cuda_sched.inl:306-320 returns without a sync): --single-frames back-to-back frame() calls, one
     # final sync, into one shared target and into two alternating targets (rank 0, N = 1)
     single_async = None
-    if world == 1 and not grouped and args.single_frames > 0:
+    if args.full and world == 1 and not grouped and args.single_frames > 0:
         sched = va.hip_sched(ctx)                            # hip_sched's default: cuda_sched's issue model
         single_async = {"frames": args.single_frames,
                         "path": "hip_sched::frame x N, end_frame without sync, then one vrh_sync: frames "
@@ -659,7 +712,7 @@ def main():
     # the eye orbiting --moving-camera degrees per frame, so no two frames of a launch share primary
     # rays (the timed frames share the scene camera, as the reference viewer's frames do at rest)
     moving = None
-    if world == 1 and not grouped and args.moving_camera > 0:
+    if args.full and world == 1 and not grouped and args.moving_camera > 0:
         nl = 3
         bases = scenes.orbit_bases(args.scene, args.moving_camera, F * nl)
         rt_m = target(F)
@@ -693,6 +746,41 @@ def main():
     mrays = total_rays / t_max / 1e6
 
     if rank == 0:
+        # the plain run's line, and the head of the --full one (rays per frame: the counting pass's, else
+        # the timed frames' mean, which the scene camera makes every frame's own count)
+        rays_per_frame = int(cstats["rays"]) if cstats else int(round(total_rays / args.steps))
+        head = {
+            "metric": "Mrays/s (primary + 8-sample AO)" if kernel == "ao" else "Mrays/s (primary)",
+            "value": round(mrays, 3),
+            "unit": "Mrays/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(t_max / args.steps * 1e3, 4),
+            "higher_is_better": True,
+            "scaling": "strong",
+            "vs_baseline": None,
+            "dtype": "f32",
+            "data": "synthetic (SURVEY.md Appendix A procedural scene, deterministic; frame numbers 1.. give distinct AO samples)",
+            "config": {
+                "workload": f"{args.scene} {W}x{H} 1 spp primary" + (" + 8 AO any-hit rays/hit (r=0.1)" if kernel == "ao" else ""),
+                "scene": args.scene, "primitives": int(len(prims)), "bvh_nodes": int(len(host.nodes)),
+                "width": W, "height": H, "ao_samples": 8 if kernel == "ao" else 0,
+                "rays_per_frame": rays_per_frame,
+                "parallelism": f"image-tile shard x{world}" + (f" ({args.shards} shards)" if args.shards else "")
+                               + (" + RCCL gather (libvrh render group)" if grouped else ""),
+                "frames_per_launch": F, "launches": launches,
+                "frame_numbers": [first_timed, first_timed + args.steps - 1],
+            },
+            "full": bool(args.full),
+            "host_build_s": round(build_s, 3),
+            "settle": settle,
+            "dumped": dumped,
+        }
+        if not args.full:
+            print(json.dumps(head), file=json_out, flush=True)
+
+    if rank == 0 and args.full:
         s_prim = TRI_BYTES if args.scene.startswith("hf") or args.scene == "cornell12" else SPHERE_BYTES
         n_box, n_prim, n_rays = float(cstats["box_tests"]), float(cstats["prim_tests"]), float(cstats["rays"])
         bytes_frame = NODE_BYTES * n_box + (s_prim + INDEX_BYTES) * n_prim + OUT_BYTES_PRIMARY * W * H
@@ -752,28 +840,7 @@ def main():
         if world == 1 and args.scene == "hf1M" and kernel == "ao" and not args.no_user_kernel and not grouped:
             user_leg = user_kernel_leg(W, H, n_rays)
         line = {
-            "metric": "Mrays/s (primary + 8-sample AO)" if kernel == "ao" else "Mrays/s (primary)",
-            "value": round(mrays, 3),
-            "unit": "Mrays/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(t_max / args.steps * 1e3, 4),
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic (SURVEY.md Appendix A procedural scene, deterministic; frame numbers 1.. give distinct AO samples)",
-            "config": {
-                "workload": f"{args.scene} {W}x{H} 1 spp primary" + (" + 8 AO any-hit rays/hit (r=0.1)" if kernel == "ao" else ""),
-                "scene": args.scene, "primitives": int(len(prims)), "bvh_nodes": int(len(host.nodes)),
-                "width": W, "height": H, "ao_samples": 8 if kernel == "ao" else 0,
-                "rays_per_frame": int(n_rays),
-                "parallelism": f"image-tile shard x{world}" + (f" ({args.shards} shards)" if args.shards else "")
-                               + (" + RCCL gather (libvrh render group)" if grouped else ""),
-                "frames_per_launch": F, "launches": launches,
-                "frame_numbers": [first_timed, first_timed + args.steps - 1],
-            },
+            **head,
             "roofline": {
                 "bound": "vmem-l1", "unit": "GB/s",
                 "achieved": round(achieved, 1) if achieved else None, "peak": peak,
@@ -819,8 +886,6 @@ def main():
             "user_kernel": user_leg,
             "user_kernel_mrays": user_leg.get("mrays") if user_leg else None,
             "user_kernel_deferred_mrays": (user_leg.get("deferred") or {}).get("mrays") if user_leg else None,
-            "host_build_s": round(build_s, 3),
-            "settle": settle,
             "verify": verify,
         }
         print(json.dumps(line), file=json_out, flush=True)

@@ -21,6 +21,24 @@ def golden():
 
 
 @pytest.fixture(scope="session")
+def golden_arrays():
+    """golden_arrays(case): the arrays of tests/golden/<case>.npz and of its part files
+    <case>.<array>.npz (make_golden.py's save_fixture splits a fixture too large for one file)."""
+    import glob
+
+    import numpy as np
+
+    def load(case):
+        d = os.path.join(ROOT, "tests", "golden")
+        arrs = {}
+        for path in [os.path.join(d, case + ".npz")] + sorted(glob.glob(os.path.join(d, case + ".*.npz"))):
+            with np.load(path) as z:
+                arrs.update({k: z[k] for k in z.files})
+        return arrs
+    return load
+
+
+@pytest.fixture(scope="session")
 def oracle_mod():
     from oracle import oracle as O
     O.build()

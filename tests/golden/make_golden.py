@@ -239,6 +239,24 @@ def frame_cases(out, rng):
             print(case, rec["hits"], rec["ao_occluded"], rec["occ_hash"], flush=True)
 
 
+MAX_FIXTURE_BYTES = 1 << 20     # no committed file is larger
+
+
+def save_fixture(case, arr):
+    """<case>.npz; a fixture that would pass MAX_FIXTURE_BYTES keeps its largest arrays in part files
+    <case>.<array>.npz of their own (conftest.py's golden_arrays loads a case with its parts)."""
+    arr = dict(arr)
+    path = os.path.join(HERE, case + ".npz")
+    np.savez_compressed(path, **arr)
+    while os.path.getsize(path) > MAX_FIXTURE_BYTES and len(arr) > 1:
+        k = max(arr, key=lambda n: arr[n].nbytes)
+        part = os.path.join(HERE, f"{case}.{k}.npz")
+        np.savez_compressed(part, **{k: arr.pop(k)})
+        assert os.path.getsize(part) <= MAX_FIXTURE_BYTES, part
+        np.savez_compressed(path, **arr)
+    assert os.path.getsize(path) <= MAX_FIXTURE_BYTES, path
+
+
 def list_cases(out):
     for case, scene, W, H, sb, frame in LIST_CASES:
         with tempfile.TemporaryDirectory() as d:
@@ -258,7 +276,7 @@ def list_cases(out):
                    "color_hash": fnv1a(arr["color"])}
             for k in ("primid_hash", "t_hash", "color_hash"):
                 assert rec[k] == info[k], (case, k, rec[k], info[k])
-            np.savez_compressed(os.path.join(HERE, case + ".npz"), **arr)
+            save_fixture(case, arr)
             out[case] = rec
             print(case, rec["hits"], rec["ao_occluded"], flush=True)
 

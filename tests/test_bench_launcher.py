@@ -108,3 +108,46 @@ def test_user_program_leg_reports_the_launch_choice(tmp_path, monkeypatch):
     assert leg["launch"] == {"waves_target": 6, "blocks_per_cu": 24, "stack_entries": 24, "grid": 6144}
     assert "error" in bench.user_program_run("bad_uk", 1920, 1080, 15_000_000)
     assert bench.user_program_run("absent_uk", 1920, 1080, 15_000_000) is None
+
+
+def test_plain_run_is_the_default_and_full_is_an_option(monkeypatch):
+    """A plain command line asks for the headline alone; --full and --dump-outputs are opt-in."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "4", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 4, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+
+
+def test_dump_outputs_writes_exact_float_arrays_within_the_budget(tmp_path, monkeypatch):
+    """--dump-outputs: float32 / float64 files holding every value exactly; buffers above the byte
+    budget keep one seeded sample of pixels, the same in every array and from run to run."""
+    import numpy as np
+    n = 1000
+    rng = np.random.default_rng(1)
+    bufs = {"color": rng.random((n, 4), dtype=np.float32), "t": rng.random(n, dtype=np.float32),
+            "prim_id": np.where(np.arange(n) % 7 == 0, 0xFFFFFFFF, np.arange(n) + (1 << 24)).astype(np.uint32),
+            "occ": rng.integers(0, 256, n).astype(np.uint8)}
+    rec = bench.dump_outputs(str(tmp_path / "whole"), bufs)
+    assert rec["pixels"] == rec["of"] == n and sorted(os.listdir(tmp_path / "whole")) == [
+        "color.npy", "occ.npy", "prim_id.npy", "t.npy"]
+    for k, a in bufs.items():
+        got = np.load(tmp_path / "whole" / (k + ".npy"))
+        assert got.dtype == (np.float64 if k == "prim_id" else np.float32) and got.shape == a.shape
+        assert np.array_equal(got.astype(a.dtype), a)
+    # 32 B per pixel + 8 for its index: a 20,000-byte budget keeps 500 of the 1000 pixels
+    monkeypatch.setattr(bench, "DUMP_BYTES", 20_000)
+    for d in ("a", "b"):
+        rec = bench.dump_outputs(str(tmp_path / d), bufs)
+    assert rec["pixels"] == 500 and rec["of"] == n
+    pix = np.load(tmp_path / "a" / "pixels.npy")
+    assert pix.dtype == np.float64 and len(np.unique(pix)) == 500 and np.all(np.diff(pix) > 0)
+    total = 0
+    for name in sorted(os.listdir(tmp_path / "a")):
+        a, b = np.load(tmp_path / "a" / name), np.load(tmp_path / "b" / name)
+        assert np.array_equal(a, b)
+        total += a.nbytes
+        if name != "pixels.npy":
+            assert np.array_equal(a.astype(bufs[name[:-4]].dtype), bufs[name[:-4]][pix.astype(np.int64)])
+    assert total <= 20_000

@@ -107,9 +107,9 @@ def list_scene(ctx, ref, scene_name):
 
 
 @pytest.mark.parametrize("case", ["list_hf64_160x90", "list_hf200_320x180", "list_cornell12_128"])
-def test_bvh_list_with_scissor_matches_reference(ctx, golden, case):
+def test_bvh_list_with_scissor_matches_reference(ctx, golden, golden_arrays, case):
     g = golden[case]
-    ref = np.load(os.path.join(HERE, "golden", case + ".npz"))
+    ref = golden_arrays(case)
     lst = list_scene(ctx, ref, g["scene"])
     assert lst.info["num_bvhs"] == 2
     out = render_ao(ctx, g["scene"], g["W"], g["H"], frame_num=g["frame"], scissor=tuple(g["scissor"]), scene=lst)

@@ -64,10 +64,10 @@ def test_frame_number_full_size_sample(oracle_mod, golden):
 
 
 @pytest.mark.parametrize("case", LIST_CASES)
-def test_bvh_list_with_scissor_matches_reference(oracle_mod, golden, case):
+def test_bvh_list_with_scissor_matches_reference(oracle_mod, golden, golden_arrays, case):
     O = oracle_mod
     g = golden[case]
-    ref = np.load(os.path.join(HERE, "golden", case + ".npz"))
+    ref = golden_arrays(case)
     members = list_members(O, ref, g["scene"])
     cam = O.scene_camera(g["scene"], g["W"], g["H"])
     out = O.render(members, cam, mode=O.VO_MODE_AO, frame_num=g["frame"], scissor=tuple(g["scissor"]))

@@ -53,7 +53,7 @@ def main():
     scene = sys.argv[3] if len(sys.argv) > 3 else "hf1M"
     kernel = sys.argv[4] if len(sys.argv) > 4 else "ao"
     fpl = int(sys.argv[5]) if len(sys.argv) > 5 else 20
-    cmd = sys.argv[6] if len(sys.argv) > 6 else "python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline"
+    cmd = sys.argv[6] if len(sys.argv) > 6 else "python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline"
     c, name = {}, None
     for sub in ("pmc_bench_tcp", "pmc_bench_hbm", "pmc_bench_wr"):
         v, n = per_launch(os.path.join(d, sub))

@@ -29,7 +29,7 @@ step() {  # name, timeout, command...
   if fatal $rc; then echo "fatal exit; stopping"; exit $rc; fi
   [ $rc = 0 ] || exit $rc
 }
-Q="--no-cpu-baseline --single-frames 0 --moving-camera 0 --no-user-kernel --no-verify"
+Q="--full --no-cpu-baseline --single-frames 0 --moving-camera 0 --no-user-kernel --no-verify"
 cfg_args() {  # cfg -> bench arguments (driver shape)
   case $1 in
     c3) echo "--steps 20 --warmup 5";;
@@ -53,7 +53,7 @@ for s in "$@"; do
              --timeout-method thread ${arg:+-k "$arg"};;
     smoke) step smoke 300 python -c "import __graft_entry__ as g; g.smoke()";;
     bench) extra="--no-cpu-baseline"; [ "$arg" = c3 ] && extra=""
-           step bench_$arg 600 python3 bench.py $(cfg_args $arg) $extra;;
+           step bench_$arg 600 python3 bench.py --full $(cfg_args $arg) $extra;;
     pmc)   a="$(cfg_args $arg) $Q"; set -- $(cfg_meta $arg); sc=$1 kn=$2 F=$3; d=$OUT/pmc_$arg
            step pmc_${arg}_tcp 300 rocprofv3 --pmc TCP_TOTAL_CACHE_ACCESSES_sum TD_TD_BUSY_sum GRBM_GUI_ACTIVE SQ_INSTS_VMEM_RD --output-format csv -d $d/pmc_bench_tcp -o run -- python3 bench.py $a
            step pmc_${arg}_hbm 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $d/pmc_bench_hbm -o run -- python3 bench.py $a
@@ -63,7 +63,7 @@ for s in "$@"; do
     mem)   a="$(cfg_args $arg) $Q"; d=$OUT/mem_$arg
            step mem_${arg}_tcc 300 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum --output-format csv -d $d/tcc -o run -- python3 bench.py $a
            step mem_${arg}_td 300 rocprofv3 --pmc TD_TD_BUSY_sum TD_TC_STALL_sum GRBM_GUI_ACTIVE --output-format csv -d $d/td -o run -- python3 bench.py $a;;
-    trace) step trace_$arg 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$arg -o run -- python3 bench.py $(cfg_args $arg) --no-cpu-baseline;;
+    trace) step trace_$arg 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$arg -o run -- python3 bench.py --full $(cfg_args $arg) --no-cpu-baseline;;
     ab)    IFS=: read -r sc libs kn <<< "$arg"
            LIBS="${libs//,/ }" SCENES=$sc KERNEL=${kn:-ao} step ab_${sc}_${kn:-ao} 900 bash tools/ab_builds.sh;;
     pmcuser) # lambda: the restated AO lambda (bench's user leg), defer: the same with deferred any_hit
