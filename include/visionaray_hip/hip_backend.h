@@ -736,6 +736,25 @@ hip_builtin_kernel make_hip_whitted_kernel(NormalBinding const& binding, BVH con
     return k;
 }
 
+// pathtracing::kernel (detail/pathtracing.inl:29-121) over make_kernel_params(binding, prims, normals,
+// materials, lights, num_bounces, epsilon, bg, ambient): up to num_bounces closest-hit rays per pixel
+// (the viewer: 10), every hit sampling its plastic material with random_sampler<float> seeded per
+// pixel and frame number; `ambient` is the environment light (the viewer: 1, 1, 1, 1), the lights of
+// `shading` are ignored.  hip_sched::frame / frames take it with pixel_sampler::uniform_type,
+// jittered_type and jittered_blend_type (progressive rendering: frame numbers 1, 2, ... into one
+// target); ssaa_type, camera matrices and render groups are refused (VRH_ERR_UNSUPPORTED)
+template <typename NormalBinding, typename BVH, typename Vec4>
+hip_builtin_kernel make_hip_pathtracing_kernel(NormalBinding const& binding, BVH const& bvh, hip_shading const& shading,
+                                               Vec4 const& bg, Vec4 const& ambient, unsigned num_bounces = 10,
+                                               float epsilon = 1e-3f)
+{
+    hip_builtin_kernel k = make_hip_simple_kernel(binding, bvh, shading, bg, ambient);
+    k.desc.kind = VRH_KERNEL_PATHTRACING;
+    k.desc.num_bounces = num_bounces;
+    k.desc.eps = epsilon;
+    return k;
+}
+
 template <unsigned N, typename NormalBinding, typename BVH, typename Vec4>
 hip_builtin_kernel make_hip_multi_hit_kernel(NormalBinding const& binding, BVH const& bvh, hip_shading const& shading,
                                              Vec4 const& bg)
@@ -827,7 +846,8 @@ public:
         {
             static_assert(hip_detail::user_kernels<K>::available,
                           "hip_sched runs the built-in kernels (make_hip_closest_hit_kernel / make_hip_ao_kernel / "
-                          "make_hip_simple_kernel / make_hip_multi_hit_kernel) through the C ABI; a user kernel "
+                          "make_hip_simple_kernel / make_hip_multi_hit_kernel / make_hip_whitted_kernel / "
+                          "make_hip_pathtracing_kernel) through the C ABI; a user kernel "
                           "(a callable) is device code: include visionaray_hip/hip_kernels.h and compile with hipcc");
             if (shard) throw std::runtime_error("hip_sched::frame: user kernels render the whole image");
             hip_detail::user_kernels<K>::frame(*ctx_, kernel, sparams, frame_num);

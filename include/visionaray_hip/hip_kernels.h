@@ -53,6 +53,7 @@
 #endif
 #include "detail/vrh_device.h"
 #include "detail/vrh_libm.h"
+#include "detail/vrh_sampler.h"
 
 #include <array>
 #include <atomic>
@@ -270,11 +271,8 @@ struct default_intersector : basic_intersector<default_intersector>
 };
 
 //-------------------------------------------------------------------------------------------------
-// random_sampler<float> (random_sampler.h:24-57): std::default_random_engine -- libstdc++'s
-// minstd_rand0, x <- 16807 x mod (2^31 - 1), seeded with seed mod (2^31 - 1) (1 for 0) -- under
-// std::uniform_real_distribution<float>(0, 1), i.e. generate_canonical<float, 24> (random.tcc:
-// one engine call; (x - 1) as float over float(2^31 - 1 + 1) = 2^31; 1.0 clamped to the float below 1)
-// times (1 - 0) plus 0.  Bit-identical to the reference's CPU sampler (tests/test_gpu_ref_kernels.py).
+// random_sampler<float> (random_sampler.h:24-57), restated in detail/vrh_sampler.h (shared with the
+// built-in path tracer): bit-identical to the reference's CPU sampler (tests/test_gpu_ref_kernels.py).
 //
 
 template <typename T> class random_sampler;
@@ -286,15 +284,9 @@ public:
     using value_type = float;
 
     VRH_FUNC random_sampler() = default;
-    VRH_FUNC random_sampler(unsigned seed) : x_(seed % 2147483647u == 0u ? 1u : seed % 2147483647u) {}
+    VRH_FUNC random_sampler(unsigned seed) : x_(vrh::dev::minstd_seed(seed)) {}
 
-    VRH_FUNC float next()
-    {
-        x_ = uint32_t((uint64_t(x_) * 16807u) % 2147483647u);
-        float r = float(x_ - 1u) / 2147483648.0f;
-        if (r >= 1.0f) r = 0.99999994f;             // std::nextafter(1.0f, 0.0f)
-        return r * (1.0f - 0.0f) + 0.0f;
-    }
+    VRH_FUNC float next() { return vrh::dev::minstd_next(x_); }
 
 private:
     uint32_t x_ = 1u;                               // default_seed
@@ -1915,22 +1907,9 @@ VRH_FUNC inline vec3 get_normal(Normals normals, HR const& hr)
 
 namespace hip_detail
 {
-// cuda_sched.inl:27-36 (the integer hash of thrust's monte_carlo example)
-__device__ inline unsigned seed_hash(unsigned a)
-{
-    a = (a + 0x7ed55d16u) + (a << 12);
-    a = (a ^ 0xc761c23cu) ^ (a >> 19);
-    a = (a + 0x165667b1u) + (a << 5);
-    a = (a + 0xd3a2646cu) ^ (a << 9);
-    a = (a + 0xfd7046c5u) + (a << 3);
-    a = (a ^ 0xb55a4f09u) ^ (a >> 16);
-    return a;
-}
-
-__device__ inline unsigned pixel_seed(unsigned x, unsigned y, unsigned w, unsigned h, unsigned frame_num)
-{
-    return seed_hash(frame_num * w * h + y * w + x);
-}
+// detail/vrh_sampler.h: cuda_sched.inl:27-36 (the integer hash of thrust's monte_carlo example)
+using vrh::dev::seed_hash;
+using vrh::dev::pixel_seed;
 } // hip_detail
 
 __device__ inline vec3 hip_ao_sample(uint32_t pixel, uint32_t s, uint32_t frame_num)

@@ -22,6 +22,7 @@
  *                         the material / light arrays, as viewer.cpp:501-523 uploads them)
  *   VRH_KERNEL_SIMPLE  <- simple::kernel<Params>                     detail/simple.inl:19-83
  *   VRH_KERNEL_WHITTED <- whitted::kernel<Params>                    detail/whitted.inl:186-277
+ *   VRH_KERNEL_PATHTRACING <- pathtracing::kernel<Params>            detail/pathtracing.inl:29-121
  *   vrh_obj_load       <- load_obj(filename, model&)                 src/common/obj_loader.cpp:299-527
  *
  * Status codes: every function returns 0 on success and never throws or longjmps across the ABI;
@@ -71,10 +72,18 @@ enum vrh_kernel_kind {
     VRH_KERNEL_MULTI_HIT = 3, /* multi_hit<N> (traverse_linear.inl:333-380, detail/multi_hit.h):
                                  the N closest hits per pixel (render-target hit lists) and the
                                  front-to-back compositing kernel of examples/multi_hit/main.cpp */
-    VRH_KERNEL_WHITTED = 4    /* whitted::kernel (detail/whitted.inl:186-277): simple::kernel's
+    VRH_KERNEL_WHITTED = 4,   /* whitted::kernel (detail/whitted.inl:186-277): simple::kernel's
                                  shading with an any-hit shadow ray per light and plastic
                                  reflections (kr 0.1) for num_bounces iterations; eps is the
                                  scene epsilon (shadow / reflection ray origin offset)       */
+    VRH_KERNEL_PATHTRACING = 5 /* pathtracing::kernel (detail/pathtracing.inl:29-121): a path of up
+                                 to num_bounces closest-hit rays per pixel, every hit sampling its
+                                 plastic material (plastic.inl:186-230) with the reference's
+                                 random_sampler<float> seeded per pixel and frame; a path that
+                                 leaves the scene is lit by `ambient` (the environment), eps
+                                 offsets the next ray's origin; the lights of `shading` are
+                                 ignored.  Triangles, a single BVH, no hit mask; samplers
+                                 uniform / jittered / jittered_blend (progressive accumulation) */
 };
 #define VRH_MAX_HITS 16
 
@@ -130,7 +139,8 @@ typedef struct {
     float    ambient[4];      /* ambient_color (RGBA; rgb scaled by a, spectrum.inl:375)   */
     const vrh_shading* shading;   /* materials + lights (vrh_shading_create)              */
     uint32_t max_hits;        /* VRH_KERNEL_MULTI_HIT: N (1..VRH_MAX_HITS)                  */
-    uint32_t num_bounces;     /* VRH_KERNEL_WHITTED: num_bounces (viewer default 4)          */
+    uint32_t num_bounces;     /* VRH_KERNEL_WHITTED: num_bounces (viewer default 4);
+                                 VRH_KERNEL_PATHTRACING: path length in rays (viewer: 10)    */
     const vrh_hit_mask* hit_mask; /* mask intersector for triangles (NULL: none)              */
 } vrh_kernel_desc;
 
@@ -433,7 +443,8 @@ VRH_API int vrh_stats_reset(vrh_ctx* ctx);
 VRH_API int vrh_get_accum_stats(vrh_ctx* ctx, vrh_accum_stats* out);           /* syncs */
 
 /* Pixel samplers of sched_params (pixel_sampler::*, sched_common.h:160-300 make_primary_rays and
- * :440-720 sample_pixel_impl) for the primary and AO kernels, one frame (`frame_num` as in
+ * :440-720 sample_pixel_impl) for the primary and AO kernels -- and, except SSAA, the path-tracing
+ * kernel, whose own draws stay those of its per-pixel random_sampler -- one frame (`frame_num` as in
  * vrh_render):
  *   UNIFORM        = vrh_render;
  *   JITTERED       the ray through (x + jx, y + jy), colour stored;

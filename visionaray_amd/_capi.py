@@ -17,6 +17,7 @@ VRH_OK, VRH_ERR_INVALID, VRH_ERR_HIP, VRH_ERR_OOM, VRH_ERR_UNSUPPORTED, VRH_ERR_
 VRH_GROUP_TIMEOUT_MS = 120000
 VRH_PRIM_TRI64, VRH_PRIM_SPHERE48 = 0, 1
 VRH_KERNEL_PRIMARY, VRH_KERNEL_AO, VRH_KERNEL_SIMPLE, VRH_KERNEL_MULTI_HIT, VRH_KERNEL_WHITTED = 0, 1, 2, 3, 4
+VRH_KERNEL_PATHTRACING = 5
 VRH_MAX_HITS = 16
 VRH_NORMALS_PER_FACE, VRH_NORMALS_PER_VERTEX = 0, 1
 VRH_RT_COLOR, VRH_RT_PRIM_ID, VRH_RT_T, VRH_RT_OCC, VRH_RT_ALL = 1, 2, 4, 8, 15

@@ -689,6 +689,20 @@ def whitted_kernel(bvh, shade, binding=normals_per_face_binding, bg=(0.0, 0.0, 0
     return k
 
 
+def pathtracing_kernel(bvh, shade, binding=normals_per_face_binding, bg=(0.0, 0.0, 0.0, 0.0),
+                       ambient=(1.0, 1.0, 1.0, 1.0), num_bounces=10, epsilon=1e-3, count_tests=False):
+    """pathtracing::kernel (detail/pathtracing.inl:29-121) over make_kernel_params(binding, prims, normals,
+    materials, lights, num_bounces, epsilon, bg, ambient): a path of up to num_bounces closest-hit rays per
+    pixel, every hit sampling its plastic material with the reference's random_sampler<float> (seeded per
+    pixel and frame number); a path that leaves the scene takes `ambient`, the environment light.  The
+    lights of `shade` are ignored.  Accumulate frames with pixel_sampler.jittered_blend_type."""
+    k = simple_kernel(bvh, shade, binding=binding, bg=bg, ambient=ambient, count_tests=count_tests)
+    k.desc.kind = capi.VRH_KERNEL_PATHTRACING
+    k.desc.num_bounces = num_bounces
+    k.desc.eps = epsilon
+    return k
+
+
 class hip_sched:
     """hip_sched<R>: drop-in for cuda_sched<R> (cuda_sched.h:25-40).
 
@@ -707,7 +721,8 @@ class hip_sched:
 
     def frame(self, kernel, sparams, frame_num=0, shard=None, sync=True):
         if not isinstance(kernel, _builtin_kernel):
-            raise TypeError("hip_sched runs built-in kernels only (closest_hit / ao / simple / multi_hit / whitted): an arbitrary "
+            raise TypeError("hip_sched runs built-in kernels only (closest_hit / ao / simple / multi_hit / whitted / pathtracing): an "
+                            "arbitrary "
                             "callable cannot cross the C ABI")
         rt = sparams.rt
         sampler = getattr(sparams, "sampler", pixel_sampler.uniform_type)
@@ -732,6 +747,7 @@ class hip_sched:
         rt.begin_frame()
         if sampler.kind != pixel_sampler.uniform_type.kind:
             # jittered / jittered_blend / ssaa<N> (sched_common.h:160-300, 440-720)
+            # (the path tracer: jittered / jittered_blend; the library refuses ssaa with VRH_ERR_UNSUPPORTED)
             if sh is not None:
                 raise ValueError("hip_sched::frame: pixel samplers other than uniform render the whole image")
             ps = capi.vrh_pixel_sampler(sampler.kind, sampler.count)

@@ -376,6 +376,11 @@ VRH_API int vrh_render_sharded(uint32_t n, vrh_group* const* groups, const vrh_s
                   "vrh_render_sharded: one kernel for every rank");
         if (groups[i]->rank == 0) root = int(i);
     }
+    if (kernels[0].kind == VRH_KERNEL_PATHTRACING)
+    {
+        set_error("vrh_render_sharded: render groups do not run the path-tracing kernel");
+        return VRH_ERR_UNSUPPORTED;
+    }
     const wire_layout wl = layout_for(fields, kernels[0]);
     if (root >= 0)
     {

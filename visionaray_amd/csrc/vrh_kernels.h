@@ -94,11 +94,14 @@ struct render_params
                               // bit 1 wave-uniform pair records fetched through the scalar cache
     dev::shade_params shade;  // VRH_KERNEL_SIMPLE / MULTI_HIT: materials, lights, normal binding, ambient
     uint32_t max_hits;        // VRH_KERNEL_MULTI_HIT: N
-    uint32_t num_bounces;     // VRH_KERNEL_WHITTED: loop iterations (eps = scene epsilon)
+    uint32_t num_bounces;     // VRH_KERNEL_WHITTED / PATHTRACING: loop iterations (eps = scene epsilon)
     uint32_t* mh_prim_id;     // [pixel][N] hit lists (render target side buffers)
     float* mh_t;
     dev::hit_mask_params hmask;   // mask intersector (vrh_hit_mask), hmask.mask == null: none
 };
+
+// register budget (waves / SIMD) of the path-tracing instances (render_unified_kernel<..., EPI 4>)
+constexpr int PATH_OCC = 5;
 
 constexpr int COUNTERS_FRAME = 208;     // u64 words reset before every frame
 constexpr int COUNTERS_LINES = 80;      // [80] L1 128-B lines, [81] wave-level vector-memory instructions, [82] 16-B requests,
@@ -127,7 +130,7 @@ struct launch_config
                        // 2: step loop over a BVH list (render_unified_kernel<..., LIST>),
                        // 3: step loop, frames in flight (render_unified_kernel<..., BATCH>: same code),
                        // 6: a pixel-sampler pass (render_unified_kernel<..., SAMPLED>)
-    int epi;           // primary epilogue: 0 plain, 1 VRH_KERNEL_SIMPLE, 2 VRH_KERNEL_MULTI_HIT, 3 VRH_KERNEL_WHITTED (triangles)
+    int epi;           // primary epilogue: 0 plain, 1 VRH_KERNEL_SIMPLE, 2 VRH_KERNEL_MULTI_HIT, 3 VRH_KERNEL_WHITTED, 4 VRH_KERNEL_PATHTRACING (triangles)
     int max_hits;      // MULTI_HIT: N (LDS hit lists)
     bool spill;        // the traversal stack continues in a global overflow block (render_unified_kernel<..., SPILL>)
     bool share;        // AO tail sharing (render_unified_kernel<..., SHARE>): one-frame AO launches at 5 waves / SIMD

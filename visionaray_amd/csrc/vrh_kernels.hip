@@ -577,7 +577,10 @@ __device__ __forceinline__ uint32_t kernarg_root()
 // streams pixels tile after tile and writes each pixel when its ray finishes.
 // EPI: primary-ray epilogue -- 0 colour = hit ? 1 : bg, 1 simple::kernel shading, 2 multi_hit<N>
 // hit lists + the multi_hit example's compositing, 3 whitted::kernel (the lane traces its pixel's
-// shadow and reflection rays one after the other before it takes the next pixel).
+// shadow and reflection rays one after the other before it takes the next pixel), 4
+// pathtracing::kernel (the lane traces its pixel's path, one closest-hit ray per bounce, the
+// sampler seeded per pixel from the camera's full image size: shards and scissor boxes draw the
+// same numbers).
 // LIST: the scene is a list of BVHs (vrh_scene_list_create), traversed one after the other per ray
 // and merged as traverse_linear.inl:76-141 does (list_next); EPI 0 only.
 // BATCH: the same code, instantiated separately for launches of several frames (vrh_render_batch,
@@ -636,6 +639,8 @@ __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params 
         whitted_lane w;
         w.shadow = 0; w.depth = 0;
         w.sm = reinterpret_cast<float*>(smem); w.base = P.stack_cap * block + tid; w.stride = block;   // EPI 3 LDS words
+        pt_lane pt;
+        pt.dst = mk3(1.0f, 1.0f, 1.0f); pt.x = 1u; pt.bounce = 0;
         for (;;)
         {
             uint64_t idle = __ballot(mode == IDLE);
@@ -666,6 +671,11 @@ __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params 
                                 w.color = mk3(0.0f, 0.0f, 0.0f); w.thr = 1.0f; w.depth = 0; w.shadow = 0;
                                 max_t = FMAX; any = false; quad = false;
                             }
+                            if constexpr (EPI == 4)
+                            {
+                                pt.dst = mk3(1.0f, 1.0f, 1.0f); pt.bounce = 0;
+                                pt.x = minstd_seed(pixel_seed(x, y, P.width, P.height, P.frame_num + fr));
+                            }
                             st.reset(); st.push(P.root); resume = NO_RESUME;
                             bk = 0; res_t = FMAX; res_prim = 0;
                             mode = PRIMARY;
@@ -681,7 +691,7 @@ __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params 
             }
             const bool busy = mode != IDLE;
             using ML = typename std::conditional<EPI == 2, mh_list, void>::type;
-            constexpr bool UV = EPI == 1 || EPI == 3;
+            constexpr bool UV = EPI == 1 || EPI == 3 || EPI == 4;
             const float mt = EPI == 3 ? max_t : FMAX;
             const bool an = EPI == 3 ? any : false;
             if (mode != IDLE)
@@ -762,6 +772,56 @@ __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params 
                         if (done)
                         {
                             if (P.color) P.color[out_o] = make_float4(w.color.x, w.color.y, w.color.z, 1.0f);
+                            mode = IDLE;
+                        }
+                    }
+                }
+                else if constexpr (EPI == 4)
+                {
+                    if (rc != 0)
+                    {
+                        // pathtracing.inl:47-118: the ray of bounce pt.bounce ended
+                        const bool hit = best_t != FMAX;
+                        if (pt.bounce == 0u)
+                        {
+                            hits_total += hit ? 1 : 0;
+                            if (P.prim_id) P.prim_id[out_o] = hit ? best_prim : 0xFFFFFFFFu;
+                            if (P.t) P.t[out_o] = hit ? best_t : -1.0f;
+                            if (P.occ) P.occ[out_o] = 0;
+                            if (COUNT) count_stores(cnt, P, out_o, ST_OCC | ST_PID | ST_T);
+                        }
+                        bool done = true;
+                        // result.hit is set by the first bounce's hit only: a primary miss, and every
+                        // pixel of a loop that never runs (num_bounces 0), keeps the background
+                        bool lit = pt.bounce != 0u;
+                        if (!hit)
+                            pt.dst = mk3(pt.dst.x * P.shade.amb[0], pt.dst.y * P.shade.amb[1], pt.dst.z * P.shade.amb[2]);
+                        else if (pt.bounce + 1u >= P.num_bounces)
+                        {
+                            // the last bounce's sample cannot reach the image: a path still alive after it
+                            // is set to 0, one killed by pdf <= 0 is 0 too
+                            lit = P.num_bounces != 0u;
+                            pt.dst = mk3(0.0f, 0.0f, 0.0f);
+                        }
+                        else
+                        {
+                            lit = true;
+                            done = !pt_bounce(P.shade, P.prims, P.normals, pt, r, best_t, best_prim, hx, P.eps);
+                        }
+                        if (!done)
+                        {
+                            pt.bounce += 1u;
+                            finite = finite_ray(r);
+                            best_t = FMAX; best_prim = 0; steps = 0;
+                            st.reset(); st.push(P.root); resume = NO_RESUME;
+                            rays_total += 1;
+                        }
+                        else
+                        {
+                            const float4 c = lit ? make_float4(pt.dst.x, pt.dst.y, pt.dst.z, 1.0f)
+                                                 : make_float4(P.bg[0], P.bg[1], P.bg[2], P.bg[3]);
+                            if (P.color) put_color<SAMPLED>(P, out_o, c);
+                            if (COUNT) count_stores(cnt, P, out_o, ST_COLOR);
                             mode = IDLE;
                         }
                     }
@@ -1177,6 +1237,17 @@ static kernel_fn pick_shade(bool count, int epi)
                  : dev::render_unified_kernel<dev::KIND_TRI, false, false, OCC, 1>;
 }
 
+// pathtracing::kernel (EPI 4, triangles): one frame, frames in flight (BATCH) and a pixel-sampler pass
+// (SAMPLED), at the default register budget and uncapped (occ 1); test counting on one-frame launches
+template <int OCC>
+static kernel_fn pick_path(bool count, int sched)
+{
+    if (sched == 6) return dev::render_unified_kernel<dev::KIND_TRI, false, false, OCC, 4, false, false, false, true>;
+    if (sched == 3) return dev::render_unified_kernel<dev::KIND_TRI, false, false, OCC, 4, false, true>;
+    if (count) return OCC == 1 ? dev::render_unified_kernel<dev::KIND_TRI, false, true, 1, 4> : nullptr;
+    return dev::render_unified_kernel<dev::KIND_TRI, false, false, OCC, 4>;
+}
+
 template <int KIND>
 static kernel_fn pick(bool ao, bool count, int occ, int sched)
 {
@@ -1213,6 +1284,7 @@ static kernel_fn select_variant(const launch_config& c)
 {
     if (c.share)
         if (kernel_fn f = c.kind == dev::KIND_TRI ? pick_share<dev::KIND_TRI>(c) : pick_share<dev::KIND_SPHERE>(c)) return f;
+    if (c.epi == 4) return c.occ == 1 ? pick_path<1>(c.count, c.sched) : pick_path<PATH_OCC>(c.count, c.sched);
     if (c.epi) return c.occ == 8 ? pick_shade<8>(c.count, c.epi) : c.occ == 6 ? pick_shade<6>(c.count, c.epi)
                     : c.occ == 5 ? pick_shade<5>(c.count, c.epi) : pick_shade<1>(c.count, c.epi);
     if (c.spill)

@@ -1007,10 +1007,17 @@ int render_sampled_impl(vrh_ctx* ctx, const vrh_scene* sc, vrh_rt* rt, const vrh
     VRH_CHECK(ctx && sc && rt && cam && k && ps, "vrh_render_sampled: null argument");
     VRH_CHECK(ps->kind <= VRH_SAMPLER_SSAA, "vrh_render_sampled: unknown pixel sampler");
     if (ps->kind == VRH_SAMPLER_UNIFORM && !inv_mats) return render_batch_impl(ctx, sc, rt, cam, 1, k, nullptr, frame_num, nullptr);
-    if (k->kind != VRH_KERNEL_PRIMARY && k->kind != VRH_KERNEL_AO)
+    if (k->kind == VRH_KERNEL_PATHTRACING && (inv_mats || ps->kind == VRH_SAMPLER_SSAA))
+    {
+        set_error(inv_mats ? "vrh_render_view: camera matrices run the primary and AO kernels, not the path tracer"
+                           : "vrh_render_sampled: the path-tracing kernel takes the uniform, jittered and jittered_blend samplers, not ssaa");
+        return VRH_ERR_UNSUPPORTED;
+    }
+    // the path tracer accumulates through the jittered samplers (the viewer's progressive mode)
+    if (k->kind != VRH_KERNEL_PRIMARY && k->kind != VRH_KERNEL_AO && k->kind != VRH_KERNEL_PATHTRACING)
     {
         set_error(inv_mats ? "vrh_render_view: camera matrices run the primary and AO kernels"
-                           : "vrh_render_sampled: jittered / ssaa samplers run the primary and AO kernels");
+                           : "vrh_render_sampled: jittered / ssaa samplers run the primary and AO kernels (jittered: the path tracer too)");
         return VRH_ERR_UNSUPPORTED;
     }
     if (ps->kind != VRH_SAMPLER_SSAA)
@@ -1099,11 +1106,12 @@ int render_batch_impl(vrh_ctx* ctx, const vrh_scene* sc, vrh_rt* rt, const vrh_c
     for (uint32_t f = 1; f < num_frames; ++f)
         VRH_CHECK(cams[f].width == cam->width && cams[f].height == cam->height, "vrh_render_batch: frames differ in size");
     VRH_CHECK(cam->width > 0 && cam->height > 0, "vrh_render: empty image");
-    VRH_CHECK(k->kind <= VRH_KERNEL_WHITTED, "vrh_render: unknown kernel kind");
+    VRH_CHECK(k->kind <= VRH_KERNEL_PATHTRACING, "vrh_render: unknown kernel kind");
     const bool ao = k->kind == VRH_KERNEL_AO;
     const bool multi = k->kind == VRH_KERNEL_MULTI_HIT;
     const bool whitted = k->kind == VRH_KERNEL_WHITTED;
-    const bool shade = k->kind == VRH_KERNEL_SIMPLE || multi || whitted;
+    const bool path = k->kind == VRH_KERNEL_PATHTRACING;
+    const bool shade = k->kind == VRH_KERNEL_SIMPLE || multi || whitted || path;
     const bool list = sc->num_roots > 1;
     if (multi)
     {
@@ -1129,6 +1137,7 @@ int render_batch_impl(vrh_ctx* ctx, const vrh_scene* sc, vrh_rt* rt, const vrh_c
         VRH_CHECK(sc->normals, "vrh_render: AO needs normals");
     }
     const vrh_hit_mask* hmask = k->hit_mask;
+    if (hmask && path) { set_error("vrh_render: the path-tracing kernel takes no hit mask"); return VRH_ERR_UNSUPPORTED; }
     if (hmask)
     {
         VRH_CHECK(hmask->ctx == ctx, "vrh_render: hit mask of another context");
@@ -1165,7 +1174,7 @@ int render_batch_impl(vrh_ctx* ctx, const vrh_scene* sc, vrh_rt* rt, const vrh_c
     lc.block = ctx->opt_block ? ctx->opt_block : ao_share ? 256 : 64;
     lc.share = ao_share;
     lc.stack_cap = int(cap);
-    lc.epi = whitted ? 3 : multi ? 2 : shade ? 1 : 0;
+    lc.epi = path ? 4 : whitted ? 3 : multi ? 2 : shade ? 1 : 0;
     lc.max_hits = multi ? int(k->max_hits) : 0;
     // every kernel runs the step loop (the round-1 item loop for sphere primary visibility measured
     // 6-9 % slower than the step loop with its round-2 defaults, profiles/r02_ab/ab18_sphere_schedule.log,
@@ -1180,9 +1189,15 @@ int render_batch_impl(vrh_ctx* ctx, const vrh_scene* sc, vrh_rt* rt, const vrh_c
     }
     // frames in flight on the step loop (primary / AO, uncounted): the BATCH instantiation
     if (lc.sched == 0 && num_frames > 1 && !lc.count && lc.epi == 0 && !hmask) lc.sched = 3;
+    if (lc.sched == 0 && num_frames > 1 && !lc.count && path) lc.sched = 3;
     // shading epilogues: no VGPR cap (their lane state spills at 6 waves/SIMD; measured faster at 4,
     // profiles/r01/shade/shade_bench.jsonl), except whitted, whose bounce surface lives in LDS (vrh_shade.h):
     // 96 VGPRs without spills, 5 waves/SIMD, +0.7-2.1 % over 4 (profiles/r03_ab/whitted/).
+    // pathtracing::kernel (its lane state is registers only: throughput, sampler word, bounce): uncapped
+    // the instances take 99-100 VGPRs (4 waves/SIMD); capped at 5 waves/SIMD (PATH_OCC, vrh_kernels.h) they
+    // fit 94 (one frame, frames in flight) / 96 (sampler pass) VGPRs with no VGPR spill and no scratch
+    // (-Rpass-analysis=kernel-resource-usage), so 5 is the default -- not compared on the GPU against 4;
+    // waves_per_simd 1 and the counting variant (163 VGPRs) run uncapped.
     // AO on the step loop (round 5, the lean lane state: no VGPR spill or scratch at 80 VGPRs, also in
     // the overflow-stack instances): 6 waves/SIMD, the LDS stack shrunk (below) to 16 entries so that 24
     // waves fit a CU, the rest in the overflow block -- hf1M +4.8 %, hf10M +8.7 % over 5 waves
@@ -1197,6 +1212,7 @@ int render_batch_impl(vrh_ctx* ctx, const vrh_scene* sc, vrh_rt* rt, const vrh_c
     const int occ_primary = (!lc.count && (lc.kind == 0 || num_frames > 1)) ? 8 : 6;
     lc.occ = ctx->opt_occ ? ctx->opt_occ : whitted ? 5 : lc.epi ? 1 : lc.ao ? occ_ao : occ_primary;
     if (sp) lc.occ = lc.ao ? 5 : 6;                    // the sampler instances exist at the defaults
+    if (path) lc.occ = (ctx->opt_occ == 1 || lc.count) ? 1 : PATH_OCC;
     if (list) lc.occ = ao ? 5 : 6;
     // tail sharing has instances for uncounted one-frame AO launches at 5 waves / SIMD only: where
     // the kernel selection (vrh_kernels.hip pick_share, asked through render_share_available) has no
@@ -1264,7 +1280,7 @@ int render_batch_impl(vrh_ctx* ctx, const vrh_scene* sc, vrh_rt* rt, const vrh_c
     // +1.8 % hf10M at 20 frames per launch (profiles/r02_ab/ab20_refill.log); simple::kernel and
     // whitted once 8 are: +1-2.5 % / +1 % (profiles/r02_ab/shade_refill.jsonl); one-frame primary
     // launches and multi_hit keep 1
-    const uint32_t refill_shade = (lc.epi == 1 || lc.epi == 3) ? 8u : 1u;
+    const uint32_t refill_shade = (lc.epi == 1 || lc.epi == 3 || lc.epi == 4) ? 8u : 1u;
     p.refill_min_primary = ctx->opt_refill ? uint32_t(ctx->opt_refill)
                          : (primary_step && num_frames > 1) ? 16u : lc.epi ? refill_shade : 1u;
     // primary visibility caps a lane's descent at 8 inner visits per step; at 8 waves / SIMD (round 5,
@@ -1357,7 +1373,7 @@ int render_batch_impl(vrh_ctx* ctx, const vrh_scene* sc, vrh_rt* rt, const vrh_c
         std::memcpy(p.shade.ambient, k->ambient, 16);
         for (int i = 0; i < 3; ++i) p.shade.amb[i] = p.shade.ambient[i] * p.shade.ambient[3];   // plastic.inl:13-16
     }
-    p.num_bounces = whitted ? k->num_bounces : 0u;
+    p.num_bounces = (whitted || path) ? k->num_bounces : 0u;
     if (hmask && sc->info.prim_kind == VRH_PRIM_TRI64)
         p.hmask = dev::hit_mask_params{ hmask->tc, hmask->mask, hmask->w, hmask->h };
     if (multi)

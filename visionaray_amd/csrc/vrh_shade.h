@@ -10,6 +10,8 @@
 #pragma once
 
 #include "visionaray_hip/detail/vrh_device.h"
+#include "visionaray_hip/detail/vrh_libm.h"
+#include "visionaray_hip/detail/vrh_sampler.h"
 
 namespace vrh {
 namespace dev {
@@ -180,6 +182,101 @@ __device__ inline void whitted_light_done(const shade_params& S, whitted_lane& w
                : plastic_shade(S.materials[w.mi], w.ld3(WL_N), w.ld3(WL_VIEW), w.ld3(WL_POS), S.lights[w.li]);
     w.st3(WL_SHADED, w.ld3(WL_SHADED) + c);
     w.li += 1u;
+}
+
+// pathtracing::kernel (detail/pathtracing.inl:29-121) as a per-lane state machine: a chain of
+// closest-hit rays, each hit sampling the plastic material for the next direction.  Between two rays
+// the lane keeps the path throughput `dst`, the state of its random_sampler<float> (seeded per pixel,
+// vrh_sampler.h pixel_seed) and the number of rays traced; the surface is consumed when the ray ends,
+// so nothing else survives a ray.
+struct pt_lane
+{
+    f3 dst;          // path throughput (`dst`), starts at 1
+    uint32_t x;      // sampler engine state
+    uint32_t bounce; // rays of this path that have ended
+};
+
+// orthonormal basis around w as lambertian / blinn::sample_f build it (brdf.h:48-54, 139-145)
+__device__ __forceinline__ void pt_basis(f3 w, f3& u, f3& v)
+{
+    v = fabsf(w.x) > fabsf(w.y) ? normalize(mk3(-w.z, 0.0f, w.x)) : normalize(mk3(0.0f, w.z, -w.y));
+    u = cross(v, w);
+}
+
+// One bounce (pathtracing.inl:73-113) for a hit at t of ray r: get_surface, two-sided normal,
+// plastic::sample_impl (plastic.inl:186-230), dst *= src * (dot(n, wi) / pdf).  Returns false when
+// the path dies (pdf <= 0: dst = 0); otherwise r is the next ray, from pos + wi * eps.
+// Draw order: u, then the lambertian branch's cosine_sample_hemisphere(next(), next()) takes its
+// SECOND argument first (the reference fixtures are g++ builds: arguments right to left), the blinn
+// branch u1 then u2 (two statements).
+__device__ inline bool pt_bounce(const shade_params& S, const float4* __restrict__ prims,
+                                 const float4* __restrict__ normals, pt_lane& w, ray_t& r, float t,
+                                 uint32_t prim_id, const hit_extra& hx, float eps)
+{
+    constexpr float PI = 3.14159265358979323846264338328e+00f;      // math.h:240-242 constants
+    constexpr float TWO_PI = 6.28318530717958647692528676656e+00f;
+    constexpr float INV_PI = 3.18309886183790691216444201928e-01f;
+    const surface_t sf = get_surface(S, prims, normals, prim_id, hx.li, hx.u, hx.v);
+    const plastic_t& m = sf.m;
+    const f3 wo = neg(r.dir);
+    const f3 n = dot(sf.gn, wo) < 0.0f ? neg(sf.sn) : sf.sn;         // faceforward, vector.inl:674-681
+    // mean_value (spectrum.inl:268-271): hadd / 3
+    float prob_diff = (((m.cd[0] + m.cd[1]) + m.cd[2]) / 3.0f) * m.kd;
+    float prob_spec = (((m.cs[0] + m.cs[1]) + m.cs[2]) / 3.0f) * m.ks;
+    const bool all_zero = prob_diff == 0.0f && prob_spec == 0.0f;
+    prob_diff = all_zero ? 0.5f : prob_diff;
+    prob_spec = all_zero ? 0.5f : prob_spec;
+    prob_diff = prob_diff / (prob_diff + prob_spec);
+    const float u = minstd_next(w.x);
+    f3 bu, bv, wi, src;
+    float pdf;
+    pt_basis(n, bu, bv);
+    if (u < prob_diff)
+    {
+        // lambertian::sample_f (brdf.h:44-62), cosine_sample_hemisphere (sampling.h:61-71)
+        const float u2 = minstd_next(w.x);
+        const float u1 = minstd_next(w.x);
+        const float rr = __builtin_sqrtf(u1);
+        const float theta = TWO_PI * u2;
+        const float sx = rr * libm::cosf(theta);
+        const float sy = rr * libm::sinf(theta);
+        const float sz = __builtin_sqrtf(tmax(0.0f, 1.0f - u1));
+        wi = normalize((sx * bu + sy * bv) + sz * n);
+        pdf = dot(n, wi) * INV_PI;
+        src = (mk3(m.cd[0], m.cd[1], m.cd[2]) * m.kd) * INV_PI;
+    }
+    else
+    {
+        // blinn::sample_f (brdf.h:128-155), returning blinn::f (brdf.h:114-126)
+        const float u1 = minstd_next(w.x);
+        const float u2 = minstd_next(w.x);
+        const float costheta = __builtin_powf(u1, 1.0f / (m.exp + 1.0f));
+        const float sintheta = __builtin_sqrtf(tmax(0.0f, 1.0f - costheta * costheta));
+        const float phi = u2 * TWO_PI;
+        const f3 h = normalize(((sintheta * libm::cosf(phi)) * bu + (sintheta * libm::sinf(phi)) * bv) + costheta * n);
+        const float d2 = 2.0f * dot(h, wo);                           // reflect(wo, h), vector.inl:683-689
+        wi = mk3(d2 * h.x, d2 * h.y, d2 * h.z) - wo;
+        const float vdoth = dot(wo, h);
+        pdf = ((m.exp + 1.0f) * __builtin_powf(costheta, m.exp)) / (((2.0f * PI) * 4.0f) * vdoth);
+        const f3 h2 = normalize(wo + wi);
+        const float hdotn = tmax(0.0f, dot(h2, n));
+        const f3 spec = mk3(m.cs[0], m.cs[1], m.cs[2]) * m.ks;
+        const float sat = tmax(0.0f, tmin(dot(wi, h2), 1.0f));
+        const float p5 = __builtin_powf(1.0f - sat, 5.0f);
+        const f3 schlick = spec + mk3(1.0f - spec.x, 1.0f - spec.y, 1.0f - spec.z) * p5;
+        const float nfactor = (m.exp + 2.0f) / (8.0f * PI);
+        src = (schlick * nfactor) * __builtin_powf(hdotn, m.exp);
+    }
+    if (pdf <= 0.0f)
+    {
+        w.dst = mk3(0.0f, 0.0f, 0.0f);
+        return false;
+    }
+    src = src * (dot(n, wi) / pdf);
+    w.dst = mk3(w.dst.x * src.x, w.dst.y * src.y, w.dst.z * src.z);
+    const f3 pos = r.ori + r.dir * t;
+    r = make_ray(pos + wi * eps, wi);
+    return true;
 }
 
 // per-lane sorted hit list of multi_hit<N> in LDS, column-major [field][entry][lane]
