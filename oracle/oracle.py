@@ -28,6 +28,7 @@ assert TRI_DTYPE.itemsize == 64 and SPHERE_DTYPE.itemsize == 48 and NODE_DTYPE.i
 
 VO_TRI, VO_SPHERE = 0, 1
 VO_MODE_PRIMARY, VO_MODE_AO, VO_MODE_SIMPLE, VO_MODE_MULTI_HIT, VO_MODE_WHITTED = 0, 1, 2, 3, 4
+VO_MODE_PATHTRACING = 5
 VO_NORMALS_PER_FACE, VO_NORMALS_PER_VERTEX = 0, 1
 VO_SAMPLER_UNIFORM, VO_SAMPLER_JITTERED, VO_SAMPLER_JITTERED_BLEND, VO_SAMPLER_SSAA = 0, 1, 2, 3
 SAMPLERS = {"uniform": (0, 0), "jittered": (1, 0), "jittered_blend": (2, 0), "ssaa2": (3, 2), "ssaa4": (3, 4),
@@ -72,7 +73,7 @@ class _Kernel(C.Structure):
                 ("bg", C.c_float * 4), ("materials", C.c_void_p), ("num_materials", C.c_int),
                 ("lights", C.c_void_p), ("num_lights", C.c_int), ("ambient", C.c_float * 4),
                 ("normal_binding", C.c_int), ("max_hits", C.c_int), ("num_bounces", C.c_int),
-                ("frame_num", C.c_uint32)]
+                ("frame_num", C.c_uint32), ("pow_shift", C.c_int)]
 
 
 _lib = None
@@ -111,6 +112,15 @@ def lib():
         L.vo_vertex_normals.argtypes = [vp, sz, vp]; L.vo_vertex_normals.restype = None
         L.vo_render_multi.argtypes = [C.POINTER(_Scene), C.POINTER(_Camera), C.POINTER(_Kernel), vp, vp, vp, C.c_int]
         L.vo_render_multi.restype = C.c_uint64
+        L.vo_render_pathtracing.argtypes = [C.POINTER(_Scene), C.POINTER(_Camera), C.POINTER(_Kernel), C.c_int, C.c_int,
+                                            vp, vp, vp, vp, vp, C.c_int]
+        L.vo_render_pathtracing.restype = C.c_int64
+        L.vo_render_sampled_paths.argtypes = [C.POINTER(_Scene), C.POINTER(_Camera), C.POINTER(_Kernel), C.c_int,
+                                              C.c_int, vp, vp, vp, vp, vp, C.c_int]
+        L.vo_render_sampled_paths.restype = C.c_int64
+        L.vo_powf.argtypes = [C.c_float, C.c_float, C.c_int]; L.vo_powf.restype = C.c_float
+        L.vo_libm_sinf.argtypes = [C.c_float]; L.vo_libm_sinf.restype = C.c_float
+        L.vo_libm_cosf.argtypes = [C.c_float]; L.vo_libm_cosf.restype = C.c_float
         _lib = L
     return _lib
 
@@ -225,7 +235,7 @@ def make_scene(name):
 
 def _structs(scene, cam, mode, samples=8, radius=0.1, eps=1e-3, bg=(0.1, 0.2, 0.3, 1.0), materials=None,
              lights=None, ambient=(0.0, 0.0, 0.0, 0.0), binding=VO_NORMALS_PER_FACE, max_hits=0, num_bounces=0,
-             hit_mask=None, frame_num=0, scissor=None):
+             hit_mask=None, frame_num=0, scissor=None, pow_shift=0):
     """scene: a Scene, or a list of Scenes = a BVH-ref list (normals of the first entry, indexed
     by prim_id over the whole list); scissor: (x0, y0, x1, y1) as cuda_sched reads it."""
     hm = None
@@ -249,7 +259,7 @@ def _structs(scene, cam, mode, samples=8, radius=0.1, eps=1e-3, bg=(0.1, 0.2, 0.
     k = _Kernel(mode, samples, radius, eps, (C.c_float * 4)(*bg),
                 _p(materials).value if materials is not None else None, 0 if materials is None else len(materials),
                 _p(lights).value if lights is not None else None, 0 if lights is None else len(lights),
-                (C.c_float * 4)(*ambient), binding, max_hits, num_bounces, frame_num)
+                (C.c_float * 4)(*ambient), binding, max_hits, num_bounces, frame_num, pow_shift)
     _structs.keep = (materials, lights, hm, hit_mask and (tc, mask), chain, members)
     return s, c, k
 
@@ -370,6 +380,35 @@ def render_whitted(scene, cam, binding, num_bounces=4, eps=1e-3, rows=None, thre
     m, lt, amb, bg = whitted_spec()
     return render(scene, cam, mode=VO_MODE_WHITTED, rows=rows, threads=threads, materials=m, lights=lt,
                   ambient=amb, bg=bg, binding=binding, num_bounces=num_bounces, eps=eps, hit_mask=hit_mask)
+
+
+def render_pathtracing(scene, cam, binding, materials, ambient, bg, num_bounces, eps, frame_num=0, rows=None,
+                       threads=0, pow_shift=0, scissor=None, sampler=None, init=(0.0, 0.0, 0.0, 0.0)):
+    """pathtracing::kernel frame (VO_MODE_PATHTRACING): `color`, `prim_id` and `t` of the first ray, the
+    total `rays`, and per pixel the ray count `nrays` and the path signature `sig` (FNV-1a over the hit
+    prim ids in order, 0xFFFFFFFF for a miss, then the ray count: tests/golden/pathtrace_ref.cpp).
+    pow_shift +1 / -1 moves every powf result one float up / down.  sampler: None (pixel centres),
+    "jittered" or "jittered_blend" onto a target holding `init` (a colour or a (W*H, 4) array)."""
+    _, _, _, _, W, H = cam
+    materials = np.ascontiguousarray(materials).view(PLASTIC_DTYPE)
+    out = {"color": np.zeros((H * W, 4), np.float32), "prim_id": np.full(H * W, 0xFFFFFFFF, np.uint32),
+           "t": np.full(H * W, -1.0, np.float32), "nrays": np.zeros(H * W, np.uint32), "sig": np.zeros(H * W, np.uint64)}
+    s, c, k = _structs(scene, cam, VO_MODE_PATHTRACING, eps=eps, bg=bg, materials=materials, ambient=ambient,
+                       binding=binding, num_bounces=num_bounces, frame_num=frame_num, scissor=scissor,
+                       pow_shift=pow_shift)
+    if sampler is None:
+        y0, y1 = rows if rows else (0, H)
+        rays = lib().vo_render_pathtracing(C.byref(s), C.byref(c), C.byref(k), y0, y1, _p(out["color"]),
+                                           _p(out["prim_id"]), _p(out["t"]), _p(out["nrays"]), _p(out["sig"]), threads)
+    else:
+        kind, count = SAMPLERS[sampler]
+        out["color"][:] = np.asarray(init, np.float32)
+        rays = lib().vo_render_sampled_paths(C.byref(s), C.byref(c), C.byref(k), kind, count, _p(out["color"]),
+                                             _p(out["prim_id"]), _p(out["t"]), _p(out["nrays"]), _p(out["sig"]), threads)
+    if rays < 0:
+        raise ValueError("render_pathtracing: the path tracer does not take this sampler")
+    out["rays"] = int(rays)
+    return out
 
 
 def render_multi(scene, cam, binding, max_hits=16, threads=0, hit_mask=None):

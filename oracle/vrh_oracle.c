@@ -5,7 +5,8 @@
  * -O2 -ffp-contract=off (no FMA contraction: SURVEY.md §7 hard part 1), float arithmetic in
  * exactly the reference's operation order.  Every function cites the reference file:line it
  * restates.  Parity of this file against the reference is checked by tests/test_oracle.py
- * (against oracle/_ref/vsnray_ref when built, and against the committed tests/golden fixtures).
+ * (against oracle/_ref/vsnray_ref when built, and against the committed tests/golden fixtures);
+ * the path tracer's by tests/test_oracle_pathtracing.py (oracle/_ref/pathtrace_ref, tests/golden/pt_*).
  */
 #include "vrh_oracle.h"
 
@@ -674,7 +675,7 @@ static inline void primary_ray(const vo_camera* cam, unsigned x, unsigned y, v3*
     primary_ray_at(cam, x, y, 0.0f, 0.0f, ori, dir);
 }
 
-typedef struct { float color[4]; uint32_t prim_id; float t; uint8_t occ; uint32_t list_index; uint32_t rays; } px_out;
+typedef struct { float color[4]; uint32_t prim_id; float t; uint8_t occ; uint32_t list_index; uint32_t rays; uint64_t sig; } px_out;
 
 /* closest_hit / any_hit over a list of BVH refs (traverse_linear.inl:76-141): each BVH traversed
  * with a fresh result and the same max_t; hr merged by update_if(result, hr, is_closer(hr, result,
@@ -696,6 +697,8 @@ static vo_hit trace(const vo_scene* s, const float o[3], const float d[3], int a
 static void shade_simple(const vo_scene* s, const vo_kernel* k, v3 ori, v3 dir, const vo_hit* hr, float out[4]);
 static void shade_whitted(const vo_scene* s, const vo_kernel* k, v3 ori, v3 dir, vo_hit hr, float out[4],
                           uint32_t* rays, vo_counters* cnt);
+static void pathtrace_pixel(const vo_scene* s, const vo_camera* cam, const vo_kernel* k, unsigned x, unsigned y,
+                            v3 ori, v3 dir, px_out* o, vo_counters* cnt);
 
 /* ao/main.cpp:183-246 with the deterministic sampler of SURVEY.md Appendix A */
 static px_out shade_pixel_at(const vo_scene* s, const vo_camera* cam, const vo_kernel* k, unsigned x, unsigned y,
@@ -703,9 +706,13 @@ static px_out shade_pixel_at(const vo_scene* s, const vo_camera* cam, const vo_k
 {
     px_out o;
     memcpy(o.color, k->bg, sizeof(o.color));
-    o.prim_id = 0xFFFFFFFFu; o.t = -1.0f; o.occ = 0; o.list_index = 0xFFFFFFFFu; o.rays = 1;
+    o.prim_id = 0xFFFFFFFFu; o.t = -1.0f; o.occ = 0; o.list_index = 0xFFFFFFFFu; o.rays = 1; o.sig = 0;
     v3 ori, dir;
     primary_ray_at(cam, x, y, ox, oy, &ori, &dir);
+    if (k->mode == VO_MODE_PATHTRACING) {
+        pathtrace_pixel(s, cam, k, x, y, ori, dir, &o, cnt);
+        return o;
+    }
     float fo[3] = { ori.x, ori.y, ori.z }, fd[3] = { dir.x, dir.y, dir.z };
     vo_hit hr = trace(s, fo, fd, 0, FLT_MAX, cnt);
     if (!hr.hit) return o;
@@ -873,6 +880,183 @@ static void shade_whitted(const vo_scene* s, const vo_kernel* k, v3 ori, v3 dir,
     out[0] = color.x; out[1] = color.y; out[2] = color.z; out[3] = 1.0f;     /* to_rgba */
 }
 
+/* ------------------------------------------------------------------------------------------ */
+/* pathtracing::kernel                                                                         */
+
+/* every powf of the path tracer: the host C library's, optionally moved one float up / down.
+ * Results the C standard fixes exactly (pow(x, 0) = pow(1, y) = 1, a zero) and non-finite ones
+ * stay, as in tests/golden/pathtrace_ref.cpp's powf. */
+__attribute__((noinline)) float vo_powf(float x, float y, int shift)
+{
+    float r = powf(x, y);
+    if (shift == 0 || y == 0.0f || x == 1.0f || r == 0.0f || !isfinite(r)) return r;
+    return nextafterf(r, shift > 0 ? INFINITY : -INFINITY);
+}
+
+/* random_sampler<float> (random_sampler.h:24-57) on a CPU: std::default_random_engine =
+ * std::minstd_rand0 = linear_congruential_engine<uint_fast32_t, 16807, 0, 2147483647> (libstdc++
+ * bits/random.h), under std::uniform_real_distribution<float>(0, 1). */
+typedef struct { uint32_t x; } rsampler;
+
+/* linear_congruential_engine::seed(s) (bits/random.tcc): with c = 0 a seed that is 0 mod m gives
+ * state 1, any other seed s mod m */
+static inline void rs_seed(rsampler* r, uint32_t seed)
+{
+    uint32_t m = seed % 2147483647u;
+    r->x = m == 0u ? 1u : m;
+}
+
+/* uniform_real_distribution<float>::operator() = generate_canonical<float, 24>(urng) * (b - a) + a
+ * (bits/random.h); generate_canonical (bits/random.tcc): the range r = max - min + 1 = 2^31 - 2 has
+ * log2 30, so m = max(1, (24 + 30 - 1) / 30) = 1 engine call; sum = float(urng() - min) * 1,
+ * tmp = float(1 * (long double)r) = 2^31 (r rounded to float), ret = sum / tmp, and a result >= 1
+ * becomes nextafter(1, 0) */
+static inline float rs_next(rsampler* r)
+{
+    r->x = (uint32_t)(((uint64_t)r->x * 16807u) % 2147483647u);     /* operator(): (a * x + c) mod m */
+    float sum = 0.0f + (float)(r->x - 1u) * 1.0f;
+    float tmp = (float)2147483646.0L;
+    float ret = sum / tmp;
+    if (ret >= 1.0f) ret = nextafterf(1.0f, 0.0f);
+    return ret * (1.0f - 0.0f) + 0.0f;
+}
+
+/* cuda_sched.inl:27-36 cuda_hash: the per-pixel seed is hash(clock + y * w + x), the clock
+ * replaced by frame_num * w * h (the fixtures' and hip_sched's convention) */
+static inline uint32_t seed_hash(uint32_t a)
+{
+    a = (a + 0x7ed55d16u) + (a << 12);
+    a = (a ^ 0xc761c23cu) ^ (a >> 19);
+    a = (a + 0x165667b1u) + (a << 5);
+    a = (a + 0xd3a2646cu) ^ (a << 9);
+    a = (a + 0xfd7046c5u) + (a << 3);
+    a = (a ^ 0xb55a4f09u) ^ (a >> 16);
+    return a;
+}
+
+static inline uint64_t sig_u32(uint64_t h, uint32_t v)
+{
+    for (int i = 0; i < 4; ++i) { h ^= (v >> (8 * i)) & 0xFFu; h *= 0x100000001b3ull; }
+    return h;
+}
+
+/* the local frame of lambertian / blinn::sample_f around w = n (brdf.h:48-54, 139-145) */
+static inline void sample_frame(v3 w, v3* u, v3* v)
+{
+    *v = fabsf(w.x) > fabsf(w.y) ? normalize(mk(-w.z, 0.0f, w.x)) : normalize(mk(0.0f, w.z, -w.y));
+    *u = cross(*v, w);
+}
+
+/* plastic::sample_impl (plastic.inl:186-230) for one active ray: picks the lambertian or the blinn
+ * lobe by u against prob_diff and returns that lobe's f; refl and pdf are the lobe's */
+static v3 plastic_sample(const vo_kernel* k, const vo_plastic* m, v3 n, v3 wo, v3* refl, float* pdf, rsampler* samp)
+{
+    const float PI = 3.14159265358979323846264338328e+00f, TWO_PI = 6.28318530717958647692528676656e+00f;
+    const float INV_PI = 3.18309886183790691216444201928e-01f;         /* math.h constants */
+    /* plastic.inl:203-211, mean_value (spectrum.inl:268-271) = hadd / 3 */
+    float prob_diff = ((m->cd[0] + m->cd[1] + m->cd[2]) / 3.0f) * m->kd;
+    float prob_spec = ((m->cs[0] + m->cs[1] + m->cs[2]) / 3.0f) * m->ks;
+    int all_zero = prob_diff == 0.0f && prob_spec == 0.0f;
+    if (all_zero) { prob_diff = 0.5f; prob_spec = 0.5f; }
+    prob_diff = prob_diff / (prob_diff + prob_spec);
+    float u = rs_next(samp);                                            /* plastic.inl:214 */
+    v3 bu, bv;
+    sample_frame(n, &bu, &bv);
+    if (u < prob_diff) {
+        /* lambertian::sample_f (brdf.h:44-62): cosine_sample_hemisphere(sampler.next(),
+         * sampler.next()) (sampling.h:61-71), g++: the second argument is drawn first */
+        float a2 = rs_next(samp);
+        float a1 = rs_next(samp);
+        float r = sqrtf(a1);
+        float theta = TWO_PI * a2;
+        float sx = r * vo_libm_cosf(theta);
+        float sy = r * vo_libm_sinf(theta);
+        float sz = sqrtf(fmax_ref(0.0f, 1.0f - a1));
+        v3 wi = normalize(add(add(smul(sx, bu), smul(sy, bv)), smul(sz, n)));
+        *refl = wi;
+        *pdf = dot(n, wi) * INV_PI;
+        return muls(muls(mk(m->cd[0], m->cd[1], m->cd[2]), m->kd), INV_PI);   /* lambertian::f, brdf.h:36-41 */
+    }
+    /* blinn::sample_f (brdf.h:128-155) */
+    float u1 = rs_next(samp);
+    float u2 = rs_next(samp);
+    float costheta = vo_powf(u1, 1.0f / (m->exp + 1.0f), k->pow_shift);
+    float sintheta = sqrtf(fmax_ref(0.0f, 1.0f - costheta * costheta));
+    float phi = u2 * TWO_PI;
+    v3 h = normalize(add(add(smul(sintheta * vo_libm_cosf(phi), bu), smul(sintheta * vo_libm_sinf(phi), bv)),
+                         smul(costheta, n)));
+    v3 wi = sub(smul(2.0f * dot(h, wo), h), wo);                        /* reflect(wo, h), vector.inl:683-688 */
+    float vdoth = dot(wo, h);
+    *refl = wi;
+    *pdf = ((m->exp + 1.0f) * vo_powf(costheta, m->exp, k->pow_shift)) / (2.0f * PI * 4.0f * vdoth);
+    /* blinn::f(n, wo, wi) (brdf.h:114-126) */
+    v3 hh = normalize(add(wo, wi));
+    float hdotn = fmax_ref(0.0f, dot(hh, n));
+    v3 spec = muls(mk(m->cs[0], m->cs[1], m->cs[2]), m->ks);
+    float sat = fmax_ref(0.0f, fmin_ref(dot(wi, hh), 1.0f));            /* saturate, math.h:454-457 */
+    float p5 = vo_powf(1.0f - sat, 5.0f, k->pow_shift);
+    v3 schlick = add(spec, muls(mk(1.0f - spec.x, 1.0f - spec.y, 1.0f - spec.z), p5));
+    float nfactor = (m->exp + 2.0f) / (8.0f * PI);
+    return muls(muls(schlick, nfactor), vo_powf(hdotn, m->exp, k->pow_shift));
+}
+
+/* detail/pathtracing.inl:29-121 for one ray (S = float: every mask is one bool).  o comes in with
+ * the background colour and the miss ids; o->rays / o->sig are the closest_hit calls and their
+ * signature. */
+static void pathtrace_pixel(const vo_scene* s, const vo_camera* cam, const vo_kernel* k, unsigned x, unsigned y,
+                            v3 ori, v3 dir, px_out* o, vo_counters* cnt)
+{
+    uint32_t W = (uint32_t)cam->width, H = (uint32_t)cam->height;
+    rsampler samp;
+    rs_seed(&samp, seed_hash(k->frame_num * W * H + (uint32_t)y * W + (uint32_t)x));
+    int active = 1, result_hit = 0;                                    /* pathtracing.inl:40-45 */
+    v3 dst = mk(1.0f, 1.0f, 1.0f);
+    uint64_t sig = 0xcbf29ce484222325ull;
+    o->rays = 0;
+    if (k->num_bounces <= 0) {
+        /* the loop never runs and no ray is traced; prim_id / t of the pixel still come from its
+         * primary ray (not counted) */
+        float fo[3] = { ori.x, ori.y, ori.z }, fd[3] = { dir.x, dir.y, dir.z };
+        vo_hit hr = trace(s, fo, fd, 0, FLT_MAX, NULL);
+        if (hr.hit) { o->prim_id = hr.prim_id; o->t = hr.t; o->list_index = hr.list_index; }
+    }
+    for (int bounce = 0; bounce < k->num_bounces; ++bounce) {
+        float fo[3] = { ori.x, ori.y, ori.z }, fd[3] = { dir.x, dir.y, dir.z };
+        vo_hit hr = trace(s, fo, fd, 0, FLT_MAX, cnt);                  /* pathtracing.inl:49 */
+        o->rays++;
+        sig = sig_u32(sig, hr.hit ? hr.prim_id : 0xFFFFFFFFu);
+        if (bounce == 0 && hr.hit) { o->prim_id = hr.prim_id; o->t = hr.t; o->list_index = hr.list_index; }
+        if (!hr.hit) {
+            /* pathtracing.inl:52-62: dst *= from_rgba(ambient_color) (spectrum.inl:375-378), exit */
+            dst = mul(dst, mk(k->ambient[0] * k->ambient[3], k->ambient[1] * k->ambient[3], k->ambient[2] * k->ambient[3]));
+            active = 0;
+            break;
+        }
+        if (bounce == 0) result_hit = 1;                                /* pathtracing.inl:65-69 */
+        v3 view = mk(-dir.x, -dir.y, -dir.z);
+        v3 gn, sn;
+        const vo_plastic* m = surface(s, k, &hr, &gn, &sn);            /* pathtracing.inl:77 */
+        v3 n = dot(gn, view) < 0.0f ? mk(-sn.x, -sn.y, -sn.z) : sn;      /* faceforward, vector.inl:674-681 */
+        v3 refl = mk(0.0f, 0.0f, 0.0f);
+        float pdf = 0.0f;
+        v3 src = plastic_sample(k, m, n, view, &refl, &pdf, &samp);    /* pathtracing.inl:91 */
+        int zero_pdf = pdf <= 0.0f;
+        src = muls(src, dot(n, refl) / pdf);                            /* pathtracing.inl:96 (plastic: not emissive) */
+        if (zero_pdf) {                                                 /* pathtracing.inl:97-106 */
+            dst = mk(0.0f, 0.0f, 0.0f);
+            active = 0;
+            break;
+        }
+        dst = mul(dst, src);
+        v3 pos = add(ori, muls(dir, hr.t));                            /* pathtracing.inl:109-112 */
+        ori = add(pos, muls(refl, k->eps));
+        dir = refl;
+    }
+    if (active) dst = mk(0.0f, 0.0f, 0.0f);                             /* pathtracing.inl:116 */
+    if (result_hit) { o->color[0] = dst.x; o->color[1] = dst.y; o->color[2] = dst.z; o->color[3] = 1.0f; }
+    o->sig = sig_u32(sig, o->rays);
+}
+
 /* examples/multi_hit/main.cpp:166-235: for every kept hit (in t order) the surface of
  * get_surface(hit_rec[i], params), plastic::shade with the FIRST light (no ambient), alpha 0.3,
  * front-to-back compositing; colour starts at 0 */
@@ -1001,20 +1185,34 @@ void vo_sampler_offsets(int kind, int count, unsigned x, unsigned y, unsigned wi
     }
 }
 
-int vo_render_sampled(const vo_scene* s, const vo_camera* cam, const vo_kernel* k, int kind, int count,
-                      float* color, uint32_t* prim_id, float* t, int threads)
+/* the scissor box of a camera clipped to its image (all zero: the whole image) */
+static void scissor_of(const vo_camera* cam, int* cx0, int* cy0, int* cx1, int* cy1)
+{
+    const unsigned* sb = cam->scissor;
+    const int whole = sb[0] == 0 && sb[1] == 0 && sb[2] == 0 && sb[3] == 0;
+    *cx0 = whole ? 0 : (int)sb[0]; *cy0 = whole ? 0 : (int)sb[1];
+    *cx1 = whole ? cam->width : (int)(sb[2] < (unsigned)cam->width ? sb[2] : (unsigned)cam->width);
+    *cy1 = whole ? cam->height : (int)(sb[3] < (unsigned)cam->height ? sb[3] : (unsigned)cam->height);
+}
+
+static int64_t render_sampled_impl(const vo_scene* s, const vo_camera* cam, const vo_kernel* k, int kind, int count,
+                                   float* color, uint32_t* prim_id, float* t, uint32_t* nrays, uint64_t* sig, int threads)
 {
     if (kind == VO_SAMPLER_SSAA && count != 2 && count != 4 && count != 8) return -1;
+    if (kind == VO_SAMPLER_SSAA && k->mode == VO_MODE_PATHTRACING) return -1;
     const int n = kind == VO_SAMPLER_SSAA ? count : 1;
     int W = cam->width;
+    int cx0, cy0, cx1, cy1;
+    scissor_of(cam, &cx0, &cy0, &cx1, &cy1);     /* pixels outside the box are not written */
+    int64_t rays = 0;
 #ifdef _OPENMP
     if (threads <= 0) threads = omp_get_max_threads();
 #else
     threads = 1;
 #endif
-    #pragma omp parallel for schedule(dynamic, 1) num_threads(threads)
-    for (int y = 0; y < cam->height; ++y) {
-        for (int x = 0; x < W; ++x) {
+    #pragma omp parallel for schedule(dynamic, 1) num_threads(threads) reduction(+:rays)
+    for (int y = cy0; y < cy1; ++y) {
+        for (int x = cx0; x < cx1; ++x) {
             size_t p = (size_t)y * W + x;
             float* dst = color + 4 * p;
             if (kind == VO_SAMPLER_SSAA) dst[0] = dst[1] = dst[2] = dst[3] = 0.0f;
@@ -1024,6 +1222,9 @@ int vo_render_sampled(const vo_scene* s, const vo_camera* cam, const vo_kernel* 
                 px_out o = shade_pixel_at(s, cam, k, (unsigned)x, (unsigned)y, ox, oy, NULL);
                 prim_id[p] = o.prim_id;
                 if (t) t[p] = o.t;
+                if (nrays) nrays[p] = o.rays;
+                if (sig) sig[p] = o.sig;
+                rays += o.rays;
                 if (kind == VO_SAMPLER_UNIFORM || kind == VO_SAMPLER_JITTERED) {
                     memcpy(dst, o.color, 16);
                 } else {
@@ -1037,7 +1238,50 @@ int vo_render_sampled(const vo_scene* s, const vo_camera* cam, const vo_kernel* 
             }
         }
     }
-    return 0;
+    return rays;
+}
+
+int vo_render_sampled(const vo_scene* s, const vo_camera* cam, const vo_kernel* k, int kind, int count,
+                      float* color, uint32_t* prim_id, float* t, int threads)
+{
+    return render_sampled_impl(s, cam, k, kind, count, color, prim_id, t, NULL, NULL, threads) < 0 ? -1 : 0;
+}
+
+int64_t vo_render_sampled_paths(const vo_scene* s, const vo_camera* cam, const vo_kernel* k, int kind, int count,
+                                float* color, uint32_t* prim_id, float* t, uint32_t* nrays, uint64_t* sig, int threads)
+{
+    return render_sampled_impl(s, cam, k, kind, count, color, prim_id, t, nrays, sig, threads);
+}
+
+int64_t vo_render_pathtracing(const vo_scene* s, const vo_camera* cam, const vo_kernel* k, int y0, int y1,
+                              float* color, uint32_t* prim_id, float* t, uint32_t* nrays, uint64_t* sig, int threads)
+{
+    if (k->mode != VO_MODE_PATHTRACING) return -1;
+    int W = cam->width;
+    int cx0, cy0, cx1, cy1;
+    scissor_of(cam, &cx0, &cy0, &cx1, &cy1);
+    if (y0 > cy0) cy0 = y0;
+    if (y1 < cy1) cy1 = y1;
+    int64_t rays = 0;
+#ifdef _OPENMP
+    if (threads <= 0) threads = omp_get_max_threads();
+#else
+    threads = 1;
+#endif
+    #pragma omp parallel for schedule(dynamic, 1) num_threads(threads) reduction(+:rays)
+    for (int y = cy0; y < cy1; ++y) {
+        for (int x = cx0; x < cx1; ++x) {
+            px_out o = shade_pixel(s, cam, k, (unsigned)x, (unsigned)y, NULL);
+            size_t p = (size_t)y * W + x;
+            if (color) memcpy(color + 4 * p, o.color, 16);
+            if (prim_id) prim_id[p] = o.prim_id;
+            if (t) t[p] = o.t;
+            if (nrays) nrays[p] = o.rays;
+            if (sig) sig[p] = o.sig;
+            rays += o.rays;
+        }
+    }
+    return rays;
 }
 
 uint64_t vo_render_pixels(const vo_scene* s, const vo_camera* cam, const vo_kernel* k,

@@ -30,7 +30,8 @@ typedef struct { uint32_t geom_id, prim_id, pad0, pad1; vo_vec3 center; float ra
 typedef struct { float bmin[3]; uint32_t first; float bmax[3]; uint32_t num_prims; } vo_node;
 
 enum { VO_TRI = 0, VO_SPHERE = 1 };
-enum { VO_MODE_PRIMARY = 0, VO_MODE_AO = 1, VO_MODE_SIMPLE = 2, VO_MODE_MULTI_HIT = 3, VO_MODE_WHITTED = 4 };
+enum { VO_MODE_PRIMARY = 0, VO_MODE_AO = 1, VO_MODE_SIMPLE = 2, VO_MODE_MULTI_HIT = 3, VO_MODE_WHITTED = 4,
+       VO_MODE_PATHTRACING = 5 };
 enum { VO_MAX_HITS = 16 };
 enum { VO_NORMALS_PER_FACE = 0, VO_NORMALS_PER_VERTEX = 1 };
 
@@ -117,7 +118,7 @@ typedef struct {
 /* matrix4.inl:209-244 inverse of a column-major 4x4 matrix, the reference's cofactor formula */
 void vo_inverse4(const float m[16], float out[16]);
 typedef struct {
-    int   mode;                           /* VO_MODE_PRIMARY | VO_MODE_AO | VO_MODE_SIMPLE */
+    int   mode;                           /* VO_MODE_* (VO_MODE_MULTI_HIT: vo_render_multi only) */
     int   samples;                        /* AO samples (8) */
     float radius;                         /* AO radius (0.1) */
     float eps;                            /* AO origin offset (1e-3) */
@@ -128,10 +129,13 @@ typedef struct {
     float ambient[4];
     int   normal_binding;                 /* VO_NORMALS_PER_FACE | VO_NORMALS_PER_VERTEX */
     int   max_hits;                       /* VO_MODE_MULTI_HIT: N (<= VO_MAX_HITS) */
-    int   num_bounces;                    /* VO_MODE_WHITTED (eps = scene epsilon) */
+    int   num_bounces;                    /* VO_MODE_WHITTED, VO_MODE_PATHTRACING (eps = scene epsilon) */
     /* frame number (cuda_sched::frame's frame_num): the AO sampler counter of frame n is
      * ((p*8 + s)*16 + k)*2 + n * 0x9E3779B1 (u32 wrap); frame 0 = SURVEY.md Appendix A */
     uint32_t frame_num;
+    /* VO_MODE_PATHTRACING: 0 = the host C library's powf; +1 / -1 moves every powf result of the
+     * path tracer one float up / down (vo_powf below), the probe tests/golden/pathtrace_ref.cpp has */
+    int   pow_shift;
 } vo_kernel;
 
 /* deterministic per-vertex normals for tests: prim k, vertex j: normalize(n_k + 0.4 * (U(b) - 0.5,
@@ -150,9 +154,34 @@ uint64_t vo_render_rows(const vo_scene* s, const vo_camera* cam, const vo_kernel
 uint64_t vo_render_multi(const vo_scene* s, const vo_camera* cam, const vo_kernel* k, float* color,
                          uint32_t* mh_prim_id, float* mh_t, int threads);
 
-/* Same, for an explicit list of pixel indices (p = y*W + x); outputs are indexed by list position. */
+/* VO_MODE_PATHTRACING: pathtracing::kernel (detail/pathtracing.inl:29-121) with plastic materials, lit by
+ * `ambient` where a path leaves the scene.  Per pixel a random_sampler<float> (std::minstd_rand0 under
+ * std::uniform_real_distribution<float>(0, 1), restated in vrh_oracle.c) seeded with
+ * hash(frame_num * W * H + y * W + x) in u32 arithmetic, W x H the camera's whole image and hash
+ * cuda_sched.inl:27-36.  Draw order of a bounce: u; then the lambertian branch gives its first draw
+ * to the SECOND argument of cosine_sample_hemisphere (g++ evaluates arguments right to left), the
+ * blinn branch draws u1, then u2.  sinf / cosf are vrh_libm.h's host build (vrh_oracle_libm.cpp),
+ * every powf goes through vo_powf.
+ * vo_render_rows / vo_render_sampled (jittered, jittered_blend; ssaa: -1) / vo_render_pixels take
+ * the mode; the two functions below also return, per pixel, the number of closest_hit calls
+ * (nrays) and the path signature (sig: FNV-1a 64 over the hit prim ids in order as little-endian
+ * u32, 0xFFFFFFFF for a miss, then the ray count), as tests/golden/pathtrace_ref.cpp computes them.
+ * prim_id / t are the first ray's (with num_bounces 0 the kernel traces no ray: nrays 0; prim_id / t
+ * then come from a primary ray that is not counted).  Returns the sum of nrays, -1 for a sampler
+ * the mode does not take. */
+float vo_powf(float x, float y, int shift);
+int64_t vo_render_pathtracing(const vo_scene* s, const vo_camera* cam, const vo_kernel* k, int y0, int y1,
+                              float* color, uint32_t* prim_id, float* t, uint32_t* nrays, uint64_t* sig, int threads);
+int64_t vo_render_sampled_paths(const vo_scene* s, const vo_camera* cam, const vo_kernel* k, int kind, int count,
+                                float* color, uint32_t* prim_id, float* t, uint32_t* nrays, uint64_t* sig, int threads);
+/* vrh_oracle_libm.cpp: sinf / cosf of include/visionaray_hip/detail/vrh_libm.h (glibc 2.35's, restated) */
+float vo_libm_sinf(float x);
+float vo_libm_cosf(float x);
+
+/* Same as vo_render_rows, for an explicit list of pixel indices (p = y*W + x); outputs are indexed by list position. */
 /* pixel samplers: VO_SAMPLER_* kind, count = ssaa samples (2, 4, 8); color is read (blend) and
- * written for the whole image, prim_id = the last sample's hit.  Returns 0, -1 for a bad count. */
+ * written for every pixel of the camera's scissor box (all zero: the whole image), prim_id = the
+ * last sample's hit.  Returns 0, -1 for a bad count (and for ssaa with VO_MODE_PATHTRACING). */
 enum { VO_SAMPLER_UNIFORM = 0, VO_SAMPLER_JITTERED = 1, VO_SAMPLER_JITTERED_BLEND = 2, VO_SAMPLER_SSAA = 3 };
 void vo_sampler_offsets(int kind, int count, unsigned x, unsigned y, unsigned width, uint32_t frame_num,
                         int sub, float* ox, float* oy);

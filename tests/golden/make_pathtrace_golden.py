@@ -77,18 +77,27 @@ def scene_of(name):
 
 
 def run_ref(scene, W, H, binding, mat_kind, bounces, first_frame, accum, pow_shift):
-    """One run of the generator: (colour snapshots, signatures, rays per pixel, closest_hit calls)."""
+    """One run of the generator on a named scene: see run_ref_arrays."""
     prims, fn, vn = scene_of(scene)
     m, bg = materials_of(mat_kind)
     eye, u, v, w, _, _ = O.scene_camera(scene, W, H)
     per_vertex = binding == "vertex"
+    return run_ref_arrays(prims, vn if per_vertex else fn, per_vertex, m, (eye, u, v, w), W, H, AMBIENT, bg, EPS,
+                          bounces, first_frame, accum, pow_shift)
+
+
+def run_ref_arrays(prims, normals, per_vertex, m, camera, W, H, ambient, bg, eps, bounces, first_frame, accum,
+                   pow_shift):
+    """One run of the generator: (colour snapshots, signatures, rays per pixel, closest_hit calls).
+    prims: 64-byte triangle records; normals: float4 rows, one per triangle (three with per_vertex);
+    m: plastic records (ca, ka, cd, kd, cs, ks, exp); camera: (eye, cam_u, cam_v, cam_w)."""
     hdr = struct.pack("<9Ii", 0x50545246, W, H, len(prims), int(per_vertex), len(m), bounces, first_frame, accum, pow_shift)
-    hdr += struct.pack("<f4f4f", EPS, *bg, *AMBIENT)
-    hdr += b"".join(np.asarray(a, np.float32).tobytes() for a in (eye, u, v, w))
+    hdr += struct.pack("<f4f4f", eps, *bg, *ambient)
+    hdr += b"".join(np.asarray(a, np.float32).tobytes() for a in camera)
     mats = np.zeros((len(m), 13), np.float32)
     for i, r in enumerate(m):
         mats[i] = list(r["ca"]) + [r["ka"]] + list(r["cd"]) + [r["kd"]] + list(r["cs"]) + [r["ks"], r["exp"]]
-    normals = np.ascontiguousarray(vn if per_vertex else fn, np.float32)
+    normals = np.ascontiguousarray(normals, np.float32)
     with tempfile.TemporaryDirectory() as d:
         src, dst = os.path.join(d, "scene.bin"), os.path.join(d, "out.bin")
         with open(src, "wb") as f:

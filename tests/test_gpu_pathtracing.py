@@ -5,7 +5,9 @@ run by make_pathtrace_golden.py) with random_sampler<float> seeded per pixel as 
 With ks = 0 (`diffuse`) no powf is reached and the GPU frame is bit-identical; with the plastics of
 whitted_spec the colour is within the fixture's rtol_spec (derived from the reference alone: twice the
 response of a frame to powf moving by one float) on at least 99 % of the hit pixels.
-EPI 4 has no overflow-stack instance (like the whitted kernel), so there is no deep-BVH case.
+EPI 4 has no overflow-stack instance (like the whitted kernel): the deep-BVH case (depth 89 with the whole
+stack in LDS, depth 999 refused on the host) and the randomized sweep against the oracle's path-tracing mode
+are in tests/test_gpu_fuzz_pathtracing.py.
 """
 import functools
 import json
