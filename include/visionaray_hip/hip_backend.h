@@ -70,8 +70,10 @@ inline void check(int rc, const char* what)
     if (rc != VRH_OK) throw hip_error(what, rc);
 }
 
-// the deepest BVH this process has taken a ref of (hip_index_bvh::ref): a user-kernel launch
-// (visionaray_hip/hip_kernels.h) gives its threads the short LDS stack while every such BVH fits it
+// the deepest BVH this process has registered -- hip_index_bvh::ref() and hip_kernels.h's checked_ref()
+// do; a hip_bvh_ref filled from vrh_scene_get_view by hand does not --: a user-kernel launch
+// (visionaray_hip/hip_kernels.h) gives its threads the short LDS stack while every such BVH fits it.
+// A launch whose stack is too short for a BVH its kernel walks is an error (hip_context::check_user_walks)
 inline std::atomic<uint32_t>& user_ref_depth()
 {
     static std::atomic<uint32_t> d{ 0u };
@@ -173,7 +175,11 @@ public:
         ctx_.reset(c, [](vrh_ctx* p) { vrh_ctx_destroy(p); });
     }
     vrh_ctx* get() const { return ctx_.get(); }
-    void sync() const { hip_detail::check(vrh_sync(get()), "vrh_sync"); }
+    void sync() const
+    {
+        hip_detail::check(vrh_sync(get()), "vrh_sync");
+        check_user_walks();
+    }
     void set_option(uint32_t opt, int64_t value)
     {
         hip_detail::check(vrh_ctx_set_option(get(), opt, value), "vrh_ctx_set_option");
@@ -197,8 +203,37 @@ public:
     {
         std::shared_ptr<void> mem;
         size_t bytes = 0;
+        uint32_t* declined = nullptr;       // vrh_ctx_user_declined, host address (once a user kernel was launched)
+        uint32_t stack_entries = 0;         // LDS stack entries per thread of the last user-kernel launch
     };
     scratch_block& scratch() { return *scratch_; }
+
+    // A user-kernel launch (hip_kernels.h) whose LDS stack is too short for a BVH its kernel walks --
+    // a hip_bvh_ref that was not registered through hip_index_bvh::ref() or checked_ref(), or a BVH
+    // deeper than VRH_USER_STACK - 1 -- declines that walk on the device and leaves the BVH's depth in
+    // the context's declined-walk word.  user_declined_word(): the word's device address for a launch
+    // with `stack_entries` entries per thread.  check_user_walks(), called by the host calls that wait
+    // for the launches (sync(), hip_buffer_rt::download): throws VRH_ERR_UNSUPPORTED once for the
+    // launches waited for, and clears the word; the context stays usable.
+    uint32_t* user_declined_word(uint32_t stack_entries)
+    {
+        uint32_t* device_word = nullptr;
+        hip_detail::check(vrh_ctx_user_declined(get(), &scratch_->declined, &device_word), "vrh_ctx_user_declined");
+        scratch_->stack_entries = stack_entries;
+        return device_word;
+    }
+    void check_user_walks() const
+    {
+        if (!scratch_->declined) return;
+        const uint32_t depth = __atomic_exchange_n(scratch_->declined, 0u, __ATOMIC_ACQUIRE);
+        if (depth == 0u) return;
+        const std::string what = "hip_sched: user kernel: a BVH of depth " + std::to_string(depth) + " needs "
+                                 + std::to_string(uint64_t(depth) + 1u) + " traversal stack entries, the launch gave "
+                                 + std::to_string(scratch_->stack_entries)
+                                 + " (register the BVH with hip_index_bvh::ref() or checked_ref(); 32 entries are the limit):"
+                                   " its closest_hit / any_hit calls were not traversed";
+        throw hip_error(what.c_str(), VRH_ERR_UNSUPPORTED);
+    }
 
     static std::shared_ptr<hip_context> const& default_context()
     {
@@ -526,6 +561,7 @@ public:
     void download(float* rgba, uint32_t* prim_id = nullptr, float* t = nullptr, uint8_t* occ = nullptr)
     {
         hip_detail::check(vrh_rt_download(ctx_->get(), rt_.get(), rgba, prim_id, t, occ), "vrh_rt_download");
+        ctx_->check_user_walks();
     }
 
     // hit lists of multi_hit<N> kernels: entry [pixel * N + k], misses 0xFFFFFFFF / -1
@@ -536,6 +572,7 @@ public:
     void download_multi_hit(uint32_t* prim_ids, float* t)
     {
         hip_detail::check(vrh_rt_download_multi_hit(ctx_->get(), rt_.get(), prim_ids, t), "vrh_rt_download_multi_hit");
+        ctx_->check_user_walks();
     }
 
     vrh_rt* handle() const { return rt_.get(); }

@@ -33,8 +33,12 @@
 // the built-in kernels' bits.
 //
 // Device lambdas capture by value ([=]): they run on the GPU.  The traversal stack lives in LDS (at most
-// VRH_USER_STACK entries per thread, VRH_USER_LDS_STACK while every BVH the program has taken a ref of
-// is shallower; below); BVHs deeper than VRH_USER_STACK are rejected by checked_ref.
+// VRH_USER_STACK entries per thread, VRH_USER_LDS_STACK while every BVH the program has registered --
+// hip_index_bvh::ref() and checked_ref() do -- is shallower; below).  A BVH of depth d needs d + 1
+// entries: checked_ref rejects one deeper than VRH_USER_STACK - 1 on the host, and a launch whose stack
+// is too short for a BVH its kernel walks (a hip_bvh_ref filled from vrh_scene_get_view and never passed
+// through checked_ref) declines the walk on the device and the host reports VRH_ERR_UNSUPPORTED at the
+// next hip_context::sync() / hip_buffer_rt::download(): an error, never a frame of misses.
 #pragma once
 
 #if !defined(__HIP__)
@@ -75,8 +79,8 @@
 #define VRH_USER_DEFER 0          // deferred any_hit calls (below), opt-in
 #endif
 #ifndef VRH_USER_LDS_STACK
-// the stack entries per thread a launch gives in LDS while every BVH the program has taken a ref of
-// (hip_index_bvh::ref) is shallower than that; once one is deeper, the depth + 1 it needs (at most
+// the stack entries per thread a launch gives in LDS while every BVH the program has registered
+// (hip_index_bvh::ref, checked_ref) is shallower than that; once one is deeper, the depth + 1 it needs (at most
 // VRH_USER_STACK).  LDS bounded the waves per CU: 64 lanes x 32 entries are 8 KB per one-wave block,
 // and a CU held fewer than 20; with 24 entries (6 KB) a CU holds 26 and the registers bound it (C3,
 // the AO lambda: 1.698 -> 1.549 ms per frame at 6 waves / SIMD, ao/main.cpp's kernel 1.662 -> 1.490;
@@ -461,14 +465,29 @@ __host__ __device__ inline P leaf_primitive(const float4* prims, uint32_t i, uin
 
 // the per-thread traversal stack: a column of the block's dynamic LDS.  With VRH_USER_LDS_STACK <
 // VRH_USER_STACK the launch gives either many entries per thread (USER_STACK_SIZED); the first LDS
-// word then holds that count (user_render writes it) and the columns start after it
+// word then holds that count (user_render writes it), the next two the address of the context's
+// declined-walk word (below), and the columns start after them
 constexpr bool USER_STACK_SIZED = VRH_USER_LDS_STACK < VRH_USER_STACK;
-constexpr uint32_t USER_LDS_HEADER = USER_STACK_SIZED ? 1u : 0u;
+constexpr uint32_t USER_LDS_HEADER = USER_STACK_SIZED ? 3u : 0u;
+constexpr uint32_t USER_LDS_TRAILER = USER_STACK_SIZED ? 0u : 2u;      // the same two words, after every other area
 __device__ inline uint32_t user_stack_entries()
 {
     extern __shared__ uint32_t vrh_user_smem[];
     if constexpr (USER_STACK_SIZED) return (uint32_t)__builtin_amdgcn_readfirstlane((int)vrh_user_smem[0]);
     return VRH_USER_STACK;
+}
+
+// A walk the launch's stack cannot hold is declined: the call returns a miss -- never an out-of-bounds
+// stack write -- and leaves the BVH's depth in the context's declined-walk word (vrh_ctx_user_declined:
+// host memory the device writes; user_render keeps its address in two LDS words), which the host turns
+// into a hip_error at the next sync() / download() (hip_backend.h hip_context::check_user_walks).  A
+// cold branch: a walk that fits executes the compare alone.
+__device__ inline uint32_t* user_declined_slot();
+__device__ __attribute__((cold)) inline void user_walk_declined(uint32_t depth)
+{
+    const uint32_t* s = user_declined_slot();
+    uint32_t* word = reinterpret_cast<uint32_t*>(uintptr_t(s[0]) | (uintptr_t(s[1]) << 32));
+    if (word) __hip_atomic_store(word, depth, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 __device__ inline vrh::dev::lds_stack user_stack()
 {
@@ -868,8 +887,9 @@ __device__ inline bool walk_quads(vrh_scene_view const& b, vrh::dev::ray_t const
     return true;
 }
 
-// the LDS stack holds VRH_USER_STACK entries: a deeper BVH (not passed through checked_ref) is not
-// traversed -- a miss, never an out-of-bounds stack write.  The hardware min/max slab test where it is
+// the LDS stack holds the launch's entries (user_stack_entries: at most VRH_USER_STACK): a BVH that
+// needs more (one not registered through ref() / checked_ref) is not traversed -- the walk is declined
+// (user_walk_declined: a miss here, an error on the host).  The hardware min/max slab test where it is
 // provably identical (vrh_device.h box_pair).  ANY: an any-hit walk (the leaf ends it at the first
 // accepted hit).  By default it is the binary walk in the reference's order, so the hit record an
 // any_hit returns is the reference's first-found one; VRH_USER_BINARY_ANYHIT=0 takes the 4-wide
@@ -882,7 +902,7 @@ __device__ inline bool walk_quads(vrh_scene_view const& b, vrh::dev::ray_t const
 template <bool ANY = false, typename Ray, typename CullT, typename Leaf>
 __device__ inline void walk(vrh_scene_view const& b, Ray const& ray, float max_t, CullT const& cull_t, Leaf&& leaf)
 {
-    if (b.max_depth >= user_stack_entries()) return;
+    if (__builtin_expect(b.max_depth >= user_stack_entries(), 0)) { user_walk_declined(b.max_depth); return; }
     const vrh::dev::ray_t r = dev_ray(ray);
     const bool fast = b.finite_bounds && vrh::dev::finite_ray(r);
     if constexpr (ANY && !VRH_USER_BINARY_ANYHIT)
@@ -1335,6 +1355,15 @@ __device__ inline uint32_t* defer_area()
     return vrh_user_smem + VRH_USER_STACK * 64u + (VRH_USER_ANYHIT_CUT ? UCUT_WORDS : 0u);
 }
 
+// the two LDS words with the address of the declined-walk word: after the stack size (USER_STACK_SIZED),
+// else behind the stacks, the entry cut's area and the deferred calls' area
+__device__ inline uint32_t* user_declined_slot()
+{
+    extern __shared__ uint32_t vrh_user_smem[];
+    if constexpr (USER_STACK_SIZED) return vrh_user_smem + 1;
+    return vrh_user_smem + VRH_USER_STACK * 64u + (VRH_USER_ANYHIT_CUT ? UCUT_WORDS : 0u) + (VRH_USER_DEFER ? DEFER_WORDS : 0u);
+}
+
 __device__ inline float4* defer_log(const uint32_t* a)
 {
     return reinterpret_cast<float4*>(uintptr_t(a[4]) | (uintptr_t(a[5]) << 32));
@@ -1355,6 +1384,7 @@ __device__ inline defer_call defer_begin(vrh_scene_view const& v, basic_ray<floa
     defer_call d{ DEFER_RUN, 0u, DTAG_NONE };
     uint32_t* a = defer_area();
     const uint32_t phase = a[0];
+    // (a BVH deeper than the stack is not deferred: the call runs, and walk() declines and records it)
     if (phase == DEFER_OFF || v.max_depth >= VRH_USER_STACK || v.num_prims >= DTAG_NONE) return d;
     const uint32_t lane = __lane_id();
     if (phase == DEFER_RECORD && a[2] == 0u)
@@ -1573,7 +1603,7 @@ VRH_FUNC inline auto intersect(
         (void)hip_detail::first_lane_ptr(view.pairs, same_bvh);
         if (same_bvh)
         {
-            if (view.max_depth >= VRH_USER_STACK) return result;
+            if (__builtin_expect(view.max_depth >= VRH_USER_STACK, 0)) { hip_detail::user_walk_declined(view.max_depth); return result; }
             const vrh::dev::ray_t r = hip_detail::dev_ray(ray);
             auto leaf2 = [&](vrh::dev::ray_t const& tr, float tmax, uint32_t i, uint32_t& flags, RT& rec) -> bool
             {
@@ -1598,7 +1628,7 @@ VRH_FUNC inline auto intersect(
                                && std::is_same<Intersector, default_intersector>::value && std::is_same<Cond, is_closer_t>::value;
     if constexpr (orderable)
     {
-        if (view.max_depth >= VRH_USER_STACK) return result;
+        if (__builtin_expect(view.max_depth >= VRH_USER_STACK, 0)) { hip_detail::user_walk_declined(view.max_depth); return result; }
         if (hip_detail::oca_wave_usable(view))
         {
             const vrh::dev::ray_t r = hip_detail::dev_ray(ray);
@@ -1705,7 +1735,7 @@ __device__ inline bvh_record traverse_bvh_direct(basic_ray<float> const& ray, vr
         (void)first_lane_ptr(b.pairs, same_bvh);
         if (same_bvh)
         {
-            if (b.max_depth >= VRH_USER_STACK) return result;
+            if (__builtin_expect(b.max_depth >= VRH_USER_STACK, 0)) { user_walk_declined(b.max_depth); return result; }
             const vrh::dev::ray_t r = dev_ray(ray);
             auto leaf2 = [&](vrh::dev::ray_t const& tr, float tmax, uint32_t i, uint32_t& flags, bvh_record& rec) -> bool
             {
@@ -1725,7 +1755,7 @@ __device__ inline bvh_record traverse_bvh_direct(basic_ray<float> const& ray, vr
     if constexpr (Any && VRH_USER_ANYHIT_ORDERED && std::is_same<Isect, default_intersector>::value)
     {
         // the ordered cooperative walk (walk_ordered): the reference's first hit, lanes sharing the work
-        if (b.max_depth >= VRH_USER_STACK) return result;
+        if (__builtin_expect(b.max_depth >= VRH_USER_STACK, 0)) { user_walk_declined(b.max_depth); return result; }
         if (oca_wave_usable(b))
         {
             const vrh::dev::ray_t r = dev_ray(ray);
@@ -1954,6 +1984,7 @@ struct user_frames
     float inv_view[16], inv_proj[16];
     char* defer_log;              // VRH_USER_DEFER: DEFER_WAVE_BYTES per block of the grid
     uint32_t stack_entries;       // LDS stack entries per thread of this launch (USER_STACK_SIZED)
+    uint32_t* declined;           // vrh_ctx_user_declined: the context's declined-walk word (user_walk_declined)
 };
 
 // the primary ray through image position (fx, fy) (the pixel plus the sampler's offset) of camera c:
@@ -2171,6 +2202,12 @@ template <typename K, uint32_t SK, uint32_t SN, uint32_t NC>
 __device__ __forceinline__ void user_render_body(K& kernel, user_frames<NC> const& f)
 {
     const uint32_t lane = threadIdx.y * 8u + threadIdx.x;
+    if (lane == 0u)
+    {
+        // where a declined walk leaves its record (user_walk_declined)
+        user_declined_slot()[0] = uint32_t(uintptr_t(f.declined));
+        user_declined_slot()[1] = uint32_t(uint64_t(uintptr_t(f.declined)) >> 32);
+    }
     if constexpr (USER_STACK_SIZED)
     {
         extern __shared__ uint32_t vrh_user_smem[];
@@ -2319,7 +2356,7 @@ inline hipError_t launch_user_render(hip_context& ctx, K const& kernel, user_fra
 {
     static_assert(!USER_STACK_SIZED || !(VRH_USER_DEFER || VRH_USER_ANYHIT_CUT || VRH_USER_ANYHIT_SHARE || VRH_USER_ANYHIT_ORDERED),
                   "the deferred calls, the entry cut and the shared / ordered any_hit walks keep their state in whole LDS stack columns");
-    // the stack the deepest BVH the program has taken a ref of needs, at least VRH_USER_LDS_STACK and at
+    // the stack the deepest BVH the program has registered (ref(), checked_ref) needs, at least VRH_USER_LDS_STACK and at
     // most VRH_USER_STACK entries per thread: fewer entries, fewer bytes of LDS per block, more blocks
     if (USER_STACK_SIZED)
     {
@@ -2329,9 +2366,10 @@ inline hipError_t launch_user_render(hip_context& ctx, K const& kernel, user_fra
     else
         f.stack_entries = VRH_USER_STACK;
     const size_t lds = (size_t(64) * f.stack_entries + USER_LDS_HEADER + (VRH_USER_ANYHIT_CUT ? UCUT_WORDS : 0u)
-                        + (VRH_USER_DEFER ? DEFER_WORDS : 0u)) * sizeof(uint32_t);
+                        + (VRH_USER_DEFER ? DEFER_WORDS : 0u) + USER_LDS_TRAILER) * sizeof(uint32_t);
     auto fn = user_render<K, SK, SN, NC>;
     check(vrh_ctx_user_queues(ctx.get(), &f.queues), "vrh_ctx_user_queues");
+    f.declined = ctx.user_declined_word(f.stack_entries);
     int dev = 0, cus = 0, per_cu = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
@@ -2487,13 +2525,17 @@ private:
 };
 } // hip_detail
 
-// the user traversal stack holds VRH_USER_STACK entries: a deeper BVH cannot be traversed (the
-// device code then reports a miss); checked_ref rejects it on the host instead
+// the user traversal stack holds at most VRH_USER_STACK entries, and a BVH of depth d needs d + 1:
+// checked_ref rejects a deeper BVH on the host, and registers the depth of one it accepts, so that the
+// launches that follow give their threads the stack it needs (as hip_index_bvh::ref() does).  A ref that
+// took neither route (a hip_bvh_ref filled from vrh_scene_get_view) renders only while it fits the short
+// stack: the device declines its walk otherwise, and the host reports it (hip_context::check_user_walks)
 template <typename Ref>
 inline Ref checked_ref(Ref r)
 {
     if (r.view.max_depth >= VRH_USER_STACK)
         throw hip_error("hip_bvh_ref: BVH deeper than VRH_USER_STACK", VRH_ERR_UNSUPPORTED);
+    hip_detail::note_ref_depth(r.view.max_depth);
     return r;
 }
 

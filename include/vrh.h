@@ -427,6 +427,15 @@ VRH_API int vrh_get_tile_times(vrh_ctx* ctx, uint64_t* out, uint64_t capacity, u
  * the context's stream before it starts.  Valid until vrh_ctx_destroy. */
 #define VRH_USER_QUEUE_STRIDE 16u
 VRH_API int vrh_ctx_user_queues(vrh_ctx* ctx, uint32_t** queues);
+/* The context's declined-walk word for the same launches: one u32 of pinned host memory that the device
+ * writes, allocated and zeroed by the first call.  A user kernel's closest_hit / any_hit on a BVH that needs
+ * more traversal stack entries than its launch gave (a view deeper than the launch's stack) is not
+ * traversed; the device stores the BVH's max_depth there instead.  After waiting for the launches
+ * (vrh_sync, vrh_rt_download) the host reads the word through host_word, reports a non-zero value as
+ * VRH_ERR_UNSUPPORTED and stores zero again (visionaray_hip/hip_backend.h hip_context::check_user_walks
+ * does).  device_word: the address kernels on the context's device use.  Either may be NULL.  Valid
+ * until vrh_ctx_destroy. */
+VRH_API int vrh_ctx_user_declined(vrh_ctx* ctx, uint32_t** host_word, uint32_t** device_word);
 
 /* accumulation over every render since the last vrh_stats_reset (hipEvents per frame, kept in a
  * ring of VRH_MAX_TIMED_FRAMES; frames beyond that are counted in rays/hits but not timed) */

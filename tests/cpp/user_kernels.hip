@@ -26,6 +26,22 @@
 //   user_kernels rsao  <grid> <W> <H> <outdir> <frame>          the AO example's kernel (ao/main.cpp:183-246)
 //                                                                with standalone.h's random_sampler and
 //                                                                cosine_sample_hemisphere; depth = hit t
+//   user_kernels deep  <grid> <W> <H> <outdir> <scenedir> <route>  the AO kernel on a BVH read from files
+//                                                                (nodes.bin, prims.bin, indices.bin,
+//                                                                normals.bin, cam.bin: eye, center, up;
+//                                                                tests/deep_cases.py), the hip_bvh_ref made
+//                                                                by <route>:
+//                                                                  ref      checked_ref(device_bvh.ref())
+//                                                                  checked  vrh_scene_get_view + checked_ref
+//                                                                  view     vrh_scene_get_view alone
+//                                                                  grow     hf<grid> through ref() (24 stack
+//                                                                           entries), then the BVH's ref()
+//                                                                           (depth + 1 entries) and its frame
+//                                                                  recover  route view, the error expected;
+//                                                                           then checked_ref on the same view
+//                                                                           and the frame
+//                                                                a hip_error: {"error_status": ..} and exit
+//                                                                status 3 (1: any other failure)
 //
 // The kernel is the reference harness's AO lambda (oracle/ref_harness.cpp run_golden, after
 // ao/main.cpp:183-246) as a user would port it to cuda_sched: closest_hit over the BVH refs, the
@@ -248,12 +264,201 @@ static auto ao_kernel_isect(ref_list refs, vec3 const* normals, unsigned W, unsi
     };
 }
 
+// the AO lambda's frame `out` (RGBA32F as rendered) decoded into the reference's four outputs:
+// prim_id.bin, t.bin, occ.bin, color.bin; box: the scissor box (x0, y0, x1, y1)
+static void write_outputs(std::string const& outdir, std::string const& mode, unsigned W, unsigned H,
+                          std::vector<float> const& out, const int (&box)[4])
+{
+    const size_t npx = size_t(W) * H;
+    std::vector<uint32_t> pid(npx);
+    std::vector<float> t(npx), color(4 * npx);
+    std::vector<uint8_t> occ(npx);
+    for (size_t p = 0; p < npx; ++p)
+    {
+        uint32_t bits;
+        memcpy(&bits, &out[4 * p], 4);
+        pid[p] = bits;
+        t[p] = out[4 * p + 1];
+        memcpy(&bits, &out[4 * p + 2], 4);
+        occ[p] = uint8_t(bits);
+        const float g = out[4 * p + 3];
+        const bool hit = pid[p] != 0xFFFFFFFFu;
+        const float c[4] = { hit ? g : 0.1f, hit ? g : 0.2f, hit ? g : 0.3f, 1.0f };
+        memcpy(&color[4 * p], c, 16);
+        const int px = int(p % W), py = int(p / W);
+        if (px < box[0] || py < box[1] || px >= box[2] || py >= box[3])
+        {
+            // outside the scissor box: the cleared target, as the reference leaves it
+            pid[p] = 0xFFFFFFFFu; t[p] = -1.0f; occ[p] = 0;
+            memset(&color[4 * p], 0, 16);
+        }
+    }
+    write_file(outdir + "/prim_id.bin", pid.data(), npx * 4);
+    write_file(outdir + "/t.bin", t.data(), npx * 4);
+    write_file(outdir + "/occ.bin", occ.data(), npx);
+    write_file(outdir + "/color.bin", color.data(), npx * 16);
+    size_t hits = 0;
+    for (auto p : pid) hits += p != 0xFFFFFFFFu;
+    printf("{\"mode\":\"%s\",\"W\":%u,\"H\":%u,\"hits\":%zu}\n", mode.c_str(), W, H, hits);
+}
+
+// a hip_error (a status of the library, or of the headers: VRH_ERR_UNSUPPORTED for a BVH deeper than the
+// traversal stack): one JSON line with the status, exit status 3; any other failure exits with 1
+static int report_hip_error(hip_error const& e)
+{
+    std::string what;
+    for (const char* c = e.what(); *c; ++c)
+    {
+        if (*c == '"' || *c == '\\') { what += '\\'; what += *c; }
+        else what += (unsigned char)(*c) < 0x20 ? ' ' : *c;
+    }
+    printf("{\"error_status\":%d,\"what\":\"%s\",\"stack_entries\":%u}\n", e.status, what.c_str(),
+           visionaray::hip_detail::last_user_launch().stack_entries);
+    fflush(stdout);
+    fprintf(stderr, "error: %s\n", e.what());
+    return 3;
+}
+
+template <typename T>
+static std::vector<T> read_file(std::string const& path)
+{
+    std::vector<T> v;
+    FILE* f = fopen(path.c_str(), "rb");
+    if (!f) { fprintf(stderr, "cannot read %s\n", path.c_str()); exit(2); }
+    fseek(f, 0, SEEK_END);
+    const long n = ftell(f);
+    fseek(f, 0, SEEK_SET);
+    if (n < 0 || size_t(n) % sizeof(T) != 0) { fprintf(stderr, "%s: not a whole number of records\n", path.c_str()); exit(2); }
+    v.resize(size_t(n) / sizeof(T));
+    if (fread(static_cast<void*>(v.data()), sizeof(T), v.size(), f) != v.size()) { fprintf(stderr, "cannot read %s\n", path.c_str()); exit(2); }
+    fclose(f);
+    return v;
+}
+
+// deep <grid> W H outdir <scenedir> <route>: the AO lambda over a BVH handed in as files, so that the
+// test decides the tree (deeper than the short LDS stack, or than the whole one) and the oracle renders
+// the same bytes.  The route is how the hip_bvh_ref the lambda captures is made (the head of this file).
+static int run_deep(int argc, char** argv, unsigned grid, unsigned W, unsigned H, std::string const& outdir)
+{
+    if (argc < 8) return 2;
+    const std::string dir = argv[6], route = argv[7];
+    using tri_t = basic_triangle<3, float>;
+    const auto prims = read_file<tri_t>(dir + "/prims.bin");
+    index_bvh<tri_t> host(prims.data(), prims.size());
+    host.nodes() = read_file<bvh_node>(dir + "/nodes.bin");
+    host.indices() = read_file<unsigned>(dir + "/indices.bin");
+    const auto normals = read_file<vec4>(dir + "/normals.bin");
+    const auto cf = read_file<float>(dir + "/cam.bin");
+    if (normals.size() != prims.size() || cf.size() != 9) { fprintf(stderr, "deep: normals.bin / cam.bin size\n"); return 2; }
+    try
+    {
+        hip_index_bvh<tri_t> dev(host, normals.data());         // vrh_scene_upload computes the depth
+        hip_buffer_rt<PF_RGBA32F, PF_UNSPECIFIED> rt;
+        rt.resize(W, H);
+        camera cam;
+        cam.perspective(45.0f * constants::degrees_to_radians<float>(), W / static_cast<float>(H), 0.001f, 1000.0f);
+        cam.look_at(vec3(cf[0], cf[1], cf[2]), vec3(cf[3], cf[4], cf[5]), vec3(cf[6], cf[7], cf[8]));
+        hip_sched<ray> sched;
+        std::vector<float> out(4 * size_t(W) * H);
+        auto const& li = visionaray::hip_detail::last_user_launch();
+        // one frame of the AO lambda over r with camera c; the download waits for it
+        auto render = [&](hip_bvh_ref const& r, camera const& c)
+        {
+            auto sp = make_sched_params(pixel_sampler::uniform_type{}, c, rt);
+            const ref_list one{ to_device(std::vector<hip_bvh_ref>{ r }), 1u };
+            sched.frame(ao_kernel(one, static_cast<vec3 const*>(r.view.normals), default_intersector{}, W, 0u), sp);
+            rt.download(out.data());
+        };
+        auto plain_view = [&]()
+        {
+            hip_bvh_ref r{};
+            hip_detail::check(vrh_scene_get_view(dev.handle(), 0, &r.view), "vrh_scene_get_view");
+            return r;
+        };
+        unsigned first_entries = 0;
+        int first_status = 0;
+        uint32_t depth = 0;
+        if (route == "ref")
+        {
+            hip_bvh_ref r = checked_ref(dev.ref());
+            depth = r.view.max_depth;
+            render(r, cam);
+        }
+        else if (route == "checked")
+        {
+            hip_bvh_ref r = plain_view();
+            depth = r.view.max_depth;
+            render(checked_ref(r), cam);
+        }
+        else if (route == "view")
+        {
+            hip_bvh_ref r = plain_view();
+            depth = r.view.max_depth;
+            render(r, cam);
+        }
+        else if (route == "grow")
+        {
+            // a shallow BVH first: the launch takes the short stack; then the first ref() of the deep one
+            std::vector<tri_t> tris(size_t(2) * grid * grid);
+            if (vrh_gen_heightfield(grid, tris.data()) != VRH_OK) return 2;
+            auto hf = build<index_bvh<tri_t>>(tris.data(), tris.size());
+            std::vector<vec4> hn(tris.size());
+            if (vrh_face_normals(tris.data(), uint32_t(tris.size()), &hn[0].x) != VRH_OK) return 2;
+            hip_index_bvh<tri_t> hf_dev(hf, hn.data());
+            camera hcam = cam;
+            hcam.look_at(vec3(0.0f, 0.9f, 1.4f), vec3(0.0f, 0.0f, 0.0f), vec3(0.0f, 1.0f, 0.0f));
+            render(checked_ref(hf_dev.ref()), hcam);
+            first_entries = li.stack_entries;
+            hip_bvh_ref r = checked_ref(dev.ref());
+            depth = r.view.max_depth;
+            render(r, cam);
+        }
+        else if (route == "recover")
+        {
+            // the unregistered view: the walk is declined and the download reports it, once; the same view
+            // through checked_ref then renders on the same context and target
+            hip_bvh_ref r = plain_view();
+            depth = r.view.max_depth;
+            try
+            {
+                render(r, cam);
+                fprintf(stderr, "recover: the unregistered view of a BVH %u deep rendered without an error\n", depth);
+                return 1;
+            }
+            catch (hip_error const& e)
+            {
+                first_status = e.status;
+                first_entries = li.stack_entries;
+            }
+            hip_context::default_context()->sync();             // reported once: nothing left to throw
+            render(checked_ref(r), cam);
+        }
+        else
+            return 2;
+        printf("{\"mode\":\"deep\",\"route\":\"%s\",\"max_depth\":%u,\"stack_entries\":%u,\"first_stack_entries\":%u,"
+               "\"first_error_status\":%d}\n", route.c_str(), depth, li.stack_entries, first_entries, first_status);
+        const int box[4] = { 0, 0, int(W), int(H) };
+        write_outputs(outdir, "deep", W, H, out, box);
+    }
+    catch (hip_error const& e)
+    {
+        return report_hip_error(e);
+    }
+    catch (std::exception const& e)
+    {
+        fprintf(stderr, "error: %s\n", e.what());
+        return 1;
+    }
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
     if (argc < 6) { fprintf(stderr, "usage: user_kernels ao|mask|heart grid W H outdir ...\n"); return 2; }
     const std::string mode = argv[1];
     const unsigned grid = unsigned(atoi(argv[2])), W = unsigned(atoi(argv[3])), H = unsigned(atoi(argv[4]));
     const std::string outdir = argv[5];
+    if (mode == "deep") return run_deep(argc, argv, grid, W, H, outdir);
     using tri_t = basic_triangle<3, float>;
     std::vector<tri_t> tris(size_t(2) * grid * grid);
     if (vrh_gen_heightfield(grid, tris.data()) != VRH_OK) return 2;
@@ -788,37 +993,11 @@ int main(int argc, char** argv)
             write_file(outdir + "/sampler_color.bin", out.data(), out.size() * 4);    // RGBA32F as rendered
             return 0;
         }
-        // decode the channels into the reference's four outputs
-        std::vector<uint32_t> pid(npx);
-        std::vector<float> t(npx), color(4 * npx);
-        std::vector<uint8_t> occ(npx);
-        for (size_t p = 0; p < npx; ++p)
-        {
-            uint32_t bits;
-            memcpy(&bits, &out[4 * p], 4);
-            pid[p] = bits;
-            t[p] = out[4 * p + 1];
-            memcpy(&bits, &out[4 * p + 2], 4);
-            occ[p] = uint8_t(bits);
-            const float g = out[4 * p + 3];
-            const bool hit = pid[p] != 0xFFFFFFFFu;
-            const float c[4] = { hit ? g : 0.1f, hit ? g : 0.2f, hit ? g : 0.3f, 1.0f };
-            memcpy(&color[4 * p], c, 16);
-            const int px = int(p % W), py = int(p / W);
-            if (px < box[0] || py < box[1] || px >= box[2] || py >= box[3])
-            {
-                // outside the scissor box: the cleared target, as the reference leaves it
-                pid[p] = 0xFFFFFFFFu; t[p] = -1.0f; occ[p] = 0;
-                memset(&color[4 * p], 0, 16);
-            }
-        }
-        write_file(outdir + "/prim_id.bin", pid.data(), npx * 4);
-        write_file(outdir + "/t.bin", t.data(), npx * 4);
-        write_file(outdir + "/occ.bin", occ.data(), npx);
-        write_file(outdir + "/color.bin", color.data(), npx * 16);
-        size_t hits = 0;
-        for (auto p : pid) hits += p != 0xFFFFFFFFu;
-        printf("{\"mode\":\"%s\",\"W\":%u,\"H\":%u,\"hits\":%zu}\n", mode.c_str(), W, H, hits);
+        write_outputs(outdir, mode, W, H, out, box);
+    }
+    catch (hip_error const& e)
+    {
+        return report_hip_error(e);
     }
     catch (std::exception const& e)
     {

@@ -144,6 +144,10 @@ def test_error_paths_without_device():
     assert b"vrh_build_bvh" in lib.vrh_last_error()
     with pytest.raises(va.VrhError):
         _capi.check("vrh_gen_heightfield", 0, None)
+    # the declined-walk word of the user-kernel launches belongs to a context
+    hw, dw = C.c_void_p(), C.c_void_p()
+    assert lib.vrh_ctx_user_declined(None, C.byref(hw), C.byref(dw)) == _capi.VRH_ERR_INVALID
+    assert b"vrh_ctx_user_declined" in lib.vrh_last_error() and not hw.value and not dw.value
     with pytest.raises(ValueError):
         va.build_index_bvh(np.zeros(0, va.TRIANGLE_DTYPE))
     if va.device_count() == 0:

@@ -11,6 +11,8 @@ import pytest
 import visionaray_amd as va
 from visionaray_amd import _capi, scenes
 
+from deep_cases import comb_bvh  # noqa: F401  (test_gpu_fuzz_pathtracing imports it from here)
+
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 FULL_CASES = ["cornell12", "hf64_160x90", "hf200_320x180", "sph5000_256x144"]
@@ -220,30 +222,6 @@ def test_edge_cases_single_leaf_zero_dir_components_and_inside_sphere(ctx, oracl
     ocam = tuple(np.array(x[:], np.float32) for x in (b.eye, b.cam_u, b.cam_v, b.cam_w)) + (32, 32)
     ref = O.render(O.Scene("s", O.VO_SPHERE, sph, sb.nodes, sb.indices, None, 0), ocam, mode=O.VO_MODE_PRIMARY)
     assert np.array_equal(got["prim_id"], ref["prim_id"]) and np.array_equal(got["t"].view(np.uint32), ref["t"].view(np.uint32))
-
-
-def comb_bvh(n):
-    """Hand-built 'comb' index BVH of depth n-1 over n triangles along x (valid reference layout):
-    inner node at level k has children (leaf: triangle k, inner: level k+1)."""
-    xs = np.arange(n, dtype=np.float32) * 0.5
-    tris = va.make_triangles(np.stack([xs, np.zeros(n), np.zeros(n)], 1), np.tile([[0.0, 0.4, 0.0]], (n, 1)),
-                             np.tile([[0.0, 0.0, 0.4]], (n, 1)))
-    nodes = np.zeros(2 * n - 1, va.BVH_NODE_DTYPE)
-
-    def box(lo, hi):
-        return [xs[lo], 0.0, 0.0], [xs[hi - 1], 0.4, 0.4]
-
-    inner = 0                       # node index of the inner node for level k
-    for k in range(n - 1):
-        c = 2 * k + 1
-        nodes[inner]["bbox_min"], nodes[inner]["bbox_max"] = box(k, n)
-        nodes[inner]["first"], nodes[inner]["num_prims"] = c, 0
-        nodes[c]["bbox_min"], nodes[c]["bbox_max"] = box(k, k + 1)
-        nodes[c]["first"], nodes[c]["num_prims"] = k, 1
-        inner = c + 1
-    nodes[inner]["bbox_min"], nodes[inner]["bbox_max"] = box(n - 1, n)
-    nodes[inner]["first"], nodes[inner]["num_prims"] = n - 1, 1
-    return tris, va.index_bvh(tris, nodes, np.arange(n, dtype=np.uint32), n - 1)
 
 
 @pytest.mark.parametrize("n", [20, 50, 90, 1000])

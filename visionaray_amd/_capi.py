@@ -161,6 +161,7 @@ SIGNATURES = {
     "vrh_get_wave_times": (C.c_int, [_vp, _vp, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
     "vrh_get_tile_times": (C.c_int, [_vp, _vp, C.c_uint64, C.POINTER(C.c_uint64)]),
     "vrh_ctx_user_queues": (C.c_int, [_vp, C.POINTER(_vp)]),
+    "vrh_ctx_user_declined": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp)]),
     "vrh_scene_list_create": (C.c_int, [_vp, C.POINTER(_vp), _u32, _vp, _u32, C.POINTER(_vp)]),
     "vrh_scene_free": (C.c_int, [_vp]),
     "vrh_scene_set_vertex_normals": (C.c_int, [_vp, _vp, _u32]),

@@ -21,6 +21,8 @@ struct vrh_ctx
     // device counters (u64), see render_params::counters; [0..7] reset per frame
     unsigned long long* counters = nullptr;
     uint32_t* user_queues = nullptr;            // vrh_ctx_user_queues (8 heads x 64 B)
+    uint32_t* user_declined = nullptr;          // vrh_ctx_user_declined: pinned host word, and its device address
+    uint32_t* user_declined_dev = nullptr;
     unsigned long long* tile_times = nullptr;   // VRH_OPT_WAVE_TIMES = 2 (counting kernels): 3 per tile
     size_t tile_times_n = 0, tile_times_used = 0;
     unsigned long long* wave_times = nullptr;   // VRH_OPT_WAVE_TIMES buffer (2 per resident wave)

@@ -148,6 +148,7 @@ VRH_API int vrh_ctx_destroy(vrh_ctx* ctx)
     if (ctx->counters) (void)hipFree(ctx->counters);
     if (ctx->wave_times) (void)hipFree(ctx->wave_times);
     if (ctx->user_queues) (void)hipFree(ctx->user_queues);
+    if (ctx->user_declined) (void)hipHostFree(ctx->user_declined);
     if (ctx->tile_times) (void)hipFree(ctx->tile_times);
     if (ctx->spill) (void)hipFree(ctx->spill);
     for (auto e : ctx->ev_start) (void)hipEventDestroy(e);
@@ -1608,6 +1609,29 @@ VRH_API int vrh_ctx_user_queues(vrh_ctx* ctx, uint32_t** queues)
         VRH_HIP(hipMalloc(&ctx->user_queues, 8u * VRH_USER_QUEUE_STRIDE * sizeof(uint32_t)));
     }
     *queues = ctx->user_queues;
+    return VRH_OK;
+}
+
+VRH_API int vrh_ctx_user_declined(vrh_ctx* ctx, uint32_t** host_word, uint32_t** device_word)
+{
+    VRH_CHECK(ctx, "vrh_ctx_user_declined: null");
+    if (!ctx->user_declined)
+    {
+        int rc = select_device(ctx);
+        if (rc) return rc;
+        // pinned, mapped, coherent host memory: a declined walk's store is the host's after the stream
+        // is waited for, with no copy per launch or per wait
+        void* h = nullptr;
+        void* d = nullptr;
+        VRH_HIP(hipHostMalloc(&h, 64, hipHostMallocMapped | hipHostMallocCoherent));
+        *static_cast<volatile uint32_t*>(h) = 0u;
+        hipError_t e = hipHostGetDevicePointer(&d, h, 0);
+        if (e != hipSuccess) { (void)hipHostFree(h); set_error(hipGetErrorString(e)); return VRH_ERR_HIP; }
+        ctx->user_declined = static_cast<uint32_t*>(h);
+        ctx->user_declined_dev = static_cast<uint32_t*>(d);
+    }
+    if (host_word) *host_word = ctx->user_declined;
+    if (device_word) *device_word = ctx->user_declined_dev;
     return VRH_OK;
 }
 
