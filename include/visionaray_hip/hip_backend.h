@@ -30,6 +30,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
+#include <iterator>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -652,6 +653,66 @@ vrh_plastic to_plastic(M const& m)
 }
 inline vrh_plastic to_plastic(vrh_plastic const& m) { return m; }
 
+// tagged records (vrh_material) from the members of a generic_material<...> pack, each through its
+// getters: plastic<float> (get_specular_exp), matte<float> (material.h: get_ca/ka/cd/kd), mirror<float>
+// (get_cr/kr/ior/absorption), emissive<float> (get_ce/ls).  The first overload that compiles wins.
+template <int N> struct rank : rank<N - 1> {};
+template <> struct rank<0> {};
+
+template <typename M>
+auto to_material(M const& m, rank<3>) -> decltype((void)m.get_specular_exp(), vrh_material())
+{
+    vrh_material g{};
+    g.kind = VRH_MATERIAL_PLASTIC;
+    g.u.plastic = to_plastic(m);
+    return g;
+}
+template <typename M>
+auto to_material(M const& m, rank<2>) -> decltype((void)m.get_ior(), vrh_material())
+{
+    vrh_material g{};
+    g.kind = VRH_MATERIAL_MIRROR;
+    rgb(m.get_cr(), g.u.mirror.cr); g.u.mirror.kr = m.get_kr();
+    rgb(m.get_ior(), g.u.mirror.ior);
+    rgb(m.get_absorption(), g.u.mirror.absorption);
+    return g;
+}
+template <typename M>
+auto to_material(M const& m, rank<1>) -> decltype((void)m.get_ls(), vrh_material())
+{
+    vrh_material g{};
+    g.kind = VRH_MATERIAL_EMISSIVE;
+    rgb(m.get_ce(), g.u.emissive.ce); g.u.emissive.ls = m.get_ls();
+    return g;
+}
+template <typename M>
+auto to_material(M const& m, rank<0>) -> decltype((void)m.get_kd(), vrh_material())
+{
+    vrh_material g{};
+    g.kind = VRH_MATERIAL_MATTE;
+    rgb(m.get_ca(), g.u.matte.ca); g.u.matte.ka = m.get_ka();
+    rgb(m.get_cd(), g.u.matte.cd); g.u.matte.kd = m.get_kd();
+    return g;
+}
+
+struct to_material_visitor
+{
+    using return_type = vrh_material;
+    template <typename X> vrh_material operator()(X const& x) const { return to_material(x, rank<3>{}); }
+};
+
+// a material list is generic when it holds vrh_material records or generic_material<...> variants
+// (generic_material.h: is_emissive() marks the variant; it is converted through the reference's own
+// apply_visitor, found by argument-dependent lookup)
+template <typename M, typename = void> struct is_generic_material : std::false_type {};
+template <> struct is_generic_material<vrh_material, void> : std::true_type {};
+template <typename M>
+struct is_generic_material<M, decltype((void)std::declval<M const&>().is_emissive())> : std::true_type {};
+
+inline vrh_material to_generic(vrh_material const& m) { return m; }
+template <typename M>
+vrh_material to_generic(M const& m) { return apply_visitor(to_material_visitor{}, m); }
+
 // point_light<float> (point_light.h:18-66) has no cl / kl getters; with the default constant
 // attenuation 1, intensity(position()) is exactly cl * kl (point_light.inl:12-28).  Other
 // attenuations: pass vrh_point_light records instead.
@@ -677,7 +738,10 @@ inline uint32_t binding_of(normals_per_face_binding const&) { return VRH_NORMALS
 inline uint32_t binding_of(normals_per_vertex_binding const&) { return VRH_NORMALS_PER_VERTEX; }
 } // hip_detail
 
-// device materials (plastic, indexed by geom_id) and point lights
+// device materials (indexed by geom_id) and point lights.  Materials: plastic<float> objects or
+// vrh_plastic records (every shading kernel); or a generic_material<...> list over plastic, matte,
+// mirror and emissive<float>, or vrh_material records -- a generic shading, which
+// make_hip_pathtracing_kernel takes and the other kernels refuse (VRH_ERR_UNSUPPORTED)
 class hip_shading
 {
 public:
@@ -686,13 +750,24 @@ public:
                 std::shared_ptr<hip_context> ctx = hip_context::default_context())
         : ctx_(std::move(ctx))
     {
-        std::vector<vrh_plastic> m;
-        for (auto const& x : materials) m.push_back(hip_detail::to_plastic(x));
+        using material_type = typename std::decay<decltype(*std::begin(materials))>::type;
         std::vector<vrh_point_light> l;
         for (auto const& x : lights) l.push_back(hip_detail::to_point_light(x));
         vrh_shading* s = nullptr;
-        hip_detail::check(vrh_shading_create(ctx_->get(), m.data(), uint32_t(m.size()), l.data(), uint32_t(l.size()), &s),
-                          "vrh_shading_create");
+        if constexpr (hip_detail::is_generic_material<material_type>::value)
+        {
+            std::vector<vrh_material> m;
+            for (auto const& x : materials) m.push_back(hip_detail::to_generic(x));
+            hip_detail::check(vrh_shading_create_generic(ctx_->get(), m.data(), uint32_t(m.size()), l.data(),
+                                                         uint32_t(l.size()), &s), "vrh_shading_create_generic");
+        }
+        else
+        {
+            std::vector<vrh_plastic> m;
+            for (auto const& x : materials) m.push_back(hip_detail::to_plastic(x));
+            hip_detail::check(vrh_shading_create(ctx_->get(), m.data(), uint32_t(m.size()), l.data(), uint32_t(l.size()), &s),
+                              "vrh_shading_create");
+        }
         shading_.reset(s, [](vrh_shading* p) { vrh_shading_free(p); });
     }
 

@@ -8,7 +8,8 @@
 //   visionaray::load_obj(filename, mod);       // obj_loader.cpp:299-527, parsed by libvrh (vrh_obj_load)
 //
 // Fills mod.primitives, shading_normals, geometric_normals, tex_coords, materials and bbox with what
-// the reference's loader stores there (appending, as the reference does).  Textures are not loaded:
+// the reference's loader stores there (appending, as the reference does).  A model whose material_type is
+// a generic_material<...> (or vrh_material) gets emissive materials where the MTL file has a Ke.  Textures are not loaded:
 // mod.texture_map / textures stay untouched.  Errors throw hip_error (the reference throws from
 // boost::iostreams on an unreadable file).
 #pragma once
@@ -41,6 +42,59 @@ auto assign_material(M& dst, vrh_plastic const& s, Vec3*)
     dst.set_ks(s.ks);
     dst.set_specular_exp(s.exp);
 }
+
+// a model whose material_type is a generic_material<...> (model.h:28; marked by is_emissive()): what
+// add_material(generic_material<Ts...>, ...) stores (obj_loader.cpp:274-296) -- emissive<float> with
+// ce = Ke, ls = 1 where the loader found length(Ke) > 0, else the plastic<float>.  The alternatives'
+// types are taken from the model's own pack (the first with set_ls, the first with set_specular_exp).
+inline void assign_material(vrh_material& dst, vrh_material const& src, void*) { dst = src; }
+
+template <typename X, typename = void> struct is_emissive_type : std::false_type {};
+template <typename X> struct is_emissive_type<X, decltype((void)std::declval<X&>().set_ls(1.0f))> : std::true_type {};
+template <typename X, typename = void> struct is_plastic_type : std::false_type {};
+template <typename X> struct is_plastic_type<X, decltype((void)std::declval<X&>().set_specular_exp(1.0f))> : std::true_type {};
+
+// the first alternative of a variant G<Ts...> that satisfies Pred (void: none)
+template <template <typename, typename> class Pred, typename... Ts> struct first_of { using type = void; };
+template <template <typename, typename> class Pred, typename X, typename... Ts>
+struct first_of<Pred, X, Ts...>
+{
+    using type = typename std::conditional<Pred<X, void>::value, X, typename first_of<Pred, Ts...>::type>::type;
+};
+template <typename G> struct alternatives;
+template <template <typename...> class G, typename... Ts>
+struct alternatives<G<Ts...>>
+{
+    using emissive_type = typename first_of<is_emissive_type, Ts...>::type;
+    using plastic_type = typename first_of<is_plastic_type, Ts...>::type;
+};
+
+template <typename M, typename Vec3>
+auto assign_material(M& dst, vrh_material const& s, Vec3*)
+    -> decltype((void)dst.is_emissive(), void())
+{
+    using E = typename alternatives<M>::emissive_type;
+    using P = typename alternatives<M>::plastic_type;
+    static_assert(!std::is_void<E>::value && !std::is_void<P>::value,
+                  "load_obj: the model's generic_material needs a plastic and an emissive alternative");
+    if (s.kind == VRH_MATERIAL_EMISSIVE)
+    {
+        E e;
+        e.set_ce(from_rgb(Vec3(s.u.emissive.ce[0], s.u.emissive.ce[1], s.u.emissive.ce[2])));
+        e.set_ls(s.u.emissive.ls);
+        dst = M(e);
+    }
+    else
+    {
+        P p;
+        assign_material(p, s.u.plastic, static_cast<Vec3*>(nullptr));
+        dst = M(p);
+    }
+}
+
+template <typename M, typename = void> struct wants_generic : std::false_type {};
+template <> struct wants_generic<vrh_material, void> : std::true_type {};
+template <typename M> struct wants_generic<M, decltype((void)std::declval<M const&>().is_emissive())> : std::true_type {};
 
 struct obj_handle
 {
@@ -91,12 +145,25 @@ void load_obj(std::string const& filename, Model& mod)
         mod.geometric_normals.push_back(normal_type(gn[4 * i], gn[4 * i + 1], gn[4 * i + 2]));
     for (size_t i = 0; i < info.num_tex_coords; ++i)
         mod.tex_coords.push_back(tex_coord_type(tc[2 * i], tc[2 * i + 1]));
-    for (auto const& p : mats)
+    if constexpr (hip_detail::wants_generic<material_type>::value)
     {
-        material_type m;
-        hip_detail::assign_material(m, p, static_cast<normal_type*>(nullptr));
-        mod.materials.push_back(m);
+        std::vector<vrh_material> gmats(info.num_materials);
+        if (!gmats.empty())
+            hip_detail::check(vrh_obj_get_generic_materials(obj.h, gmats.data()), "vrh_obj_get_generic_materials");
+        for (auto const& g : gmats)
+        {
+            material_type m;
+            hip_detail::assign_material(m, g, static_cast<normal_type*>(nullptr));
+            mod.materials.push_back(m);
+        }
     }
+    else
+        for (auto const& p : mats)
+        {
+            material_type m;
+            hip_detail::assign_material(m, p, static_cast<normal_type*>(nullptr));
+            mod.materials.push_back(m);
+        }
     mod.bbox = decltype(mod.bbox)(normal_type(info.bbox_min[0], info.bbox_min[1], info.bbox_min[2]),
                                   normal_type(info.bbox_max[0], info.bbox_max[1], info.bbox_max[2]));
 }

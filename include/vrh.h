@@ -20,6 +20,7 @@
  *   vrh_shading_create <- make_kernel_params(binding, prims, normals, materials, lights, ...)
  *                                                                     kernels.h:357-389 (device copies of
  *                         the material / light arrays, as viewer.cpp:501-523 uploads them)
+ *   vrh_shading_create_generic <- the same with generic_material<...> materials  generic_material.h
  *   VRH_KERNEL_SIMPLE  <- simple::kernel<Params>                     detail/simple.inl:19-83
  *   VRH_KERNEL_WHITTED <- whitted::kernel<Params>                    detail/whitted.inl:186-277
  *   VRH_KERNEL_PATHTRACING <- pathtracing::kernel<Params>            detail/pathtracing.inl:29-121
@@ -78,12 +79,17 @@ enum vrh_kernel_kind {
                                  scene epsilon (shadow / reflection ray origin offset)       */
     VRH_KERNEL_PATHTRACING = 5 /* pathtracing::kernel (detail/pathtracing.inl:29-121): a path of up
                                  to num_bounces closest-hit rays per pixel, every hit sampling its
-                                 plastic material (plastic.inl:186-230) with the reference's
-                                 random_sampler<float> seeded per pixel and frame; a path that
-                                 leaves the scene is lit by `ambient` (the environment), eps
-                                 offsets the next ray's origin; the lights of `shading` are
-                                 ignored.  Triangles, a single BVH, no hit mask; samplers
-                                 uniform / jittered / jittered_blend (progressive accumulation) */
+                                 material with the reference's random_sampler<float> seeded per
+                                 pixel and frame: plastic (plastic.inl:186-230) with a shading of
+                                 vrh_shading_create; plastic, matte, mirror or emissive by the
+                                 record's kind (generic_material, detail/generic_material.inl)
+                                 with a shading of vrh_shading_create_generic -- a path that
+                                 hits an emissive surface ends there and keeps its radiance.  A
+                                 path that leaves the scene is lit by `ambient` (the
+                                 environment), eps offsets the next ray's origin; the lights of
+                                 `shading` are ignored.  Triangles, a single BVH, no hit mask;
+                                 samplers uniform / jittered / jittered_blend (progressive
+                                 accumulation) */
 };
 #define VRH_MAX_HITS 16
 
@@ -99,6 +105,30 @@ typedef struct { float ca[3]; float ka; float cd[3]; float kd; float cs[3]; floa
 /* point_light<float> (point_light.h:18-66, detail/point_light.inl): intensity cl * kl with
  * attenuation 1 / (constant + linear * d + quadratic * d * d) */
 typedef struct { float position[3]; float cl[3]; float kl; float constant_att, linear_att, quadratic_att; } vrh_point_light;
+
+/* generic_material<plastic, matte, mirror, emissive> (generic_material.h, detail/generic_material.inl):
+ * a tagged record of 64 bytes, the kind word at offset 0 and the kind's parameters from offset 4 on
+ * (unused words are ignored; a device lane fetches a record as four 16-byte loads).
+ *   matte    (material.h, detail/material/matte.inl): ambient ca * ka, lambertian diffuse cd * kd
+ *   mirror   (detail/material/mirror.inl, brdf.h:163-211): specular reflection cr * kr weighted by the
+ *            conductor fresnel reflectance of (ior, absorption) per channel (fresnel.h:18-35)
+ *   emissive (detail/material/emissive.inl): radiance ce * ls; a path ends on it */
+enum vrh_material_kind {
+    VRH_MATERIAL_PLASTIC = 0,
+    VRH_MATERIAL_MATTE = 1,
+    VRH_MATERIAL_MIRROR = 2,
+    VRH_MATERIAL_EMISSIVE = 3
+};
+typedef struct {
+    uint32_t kind;            /* vrh_material_kind */
+    union {
+        vrh_plastic plastic;                                                  /* 13 floats */
+        struct { float ca[3]; float ka; float cd[3]; float kd; } matte;
+        struct { float cr[3]; float kr; float ior[3]; float absorption[3]; } mirror;
+        struct { float ce[3]; float ls; } emissive;
+        float params[15];
+    } u;
+} vrh_material;
 
 enum vrh_rt_flags {
     VRH_RT_COLOR = 1u,        /* RGBA32F colour (pixel_access.h:582-604 store)             */
@@ -375,10 +405,16 @@ VRH_API int vrh_scene_free(vrh_scene* scene);
  * the normals_per_vertex_binding array of get_shading_normal.h:64-84 */
 VRH_API int vrh_scene_set_vertex_normals(vrh_scene* scene, const void* normals, uint32_t num_normals);
 
-/* materials (plastic, indexed by geom_id) and point lights of VRH_KERNEL_SIMPLE, copied to the
- * device; referenced by vrh_kernel_desc.shading */
+/* materials (plastic, indexed by geom_id) and point lights of the shading kernels (SIMPLE, MULTI_HIT,
+ * WHITTED, PATHTRACING), copied to the device; referenced by vrh_kernel_desc.shading */
 VRH_API int vrh_shading_create(vrh_ctx* ctx, const vrh_plastic* materials, uint32_t num_materials,
                                const vrh_point_light* lights, uint32_t num_lights, vrh_shading** out);
+/* the same with tagged material records (a generic_material model): accepted by VRH_KERNEL_PATHTRACING
+ * only -- the simple, whitted and multi_hit kernels return VRH_ERR_UNSUPPORTED for it.  A record whose
+ * kind is none of vrh_material_kind -> VRH_ERR_INVALID.  A shading of plastic records alone renders the
+ * bits of vrh_shading_create's. */
+VRH_API int vrh_shading_create_generic(vrh_ctx* ctx, const vrh_material* materials, uint32_t num_materials,
+                                       const vrh_point_light* lights, uint32_t num_lights, vrh_shading** out);
 VRH_API int vrh_shading_free(vrh_shading* shading);
 
 /* render targets.  vrh_rt_alloc owns its buffers (flags = vrh_rt_flags); vrh_rt_wrap borrows
@@ -660,6 +696,10 @@ VRH_API int vrh_obj_get_info(const vrh_obj* obj, vrh_obj_info* info);
  * materials num_materials entries */
 VRH_API int vrh_obj_get_data(const vrh_obj* obj, void* triangles, float* geometric_normals,
                              float* shading_normals, float* tex_coords, vrh_plastic* materials);
+/* the materials as a generic_material model gets them (obj_loader.cpp:274-296): material i is
+ * emissive{ce = Ke, ls = 1} when length(Ke) > 0, else the plastic record of vrh_obj_get_data (padding
+ * materials are plastic); `materials` holds num_materials records */
+VRH_API int vrh_obj_get_generic_materials(const vrh_obj* obj, vrh_material* materials);
 VRH_API const char* vrh_obj_material_name(const vrh_obj* obj, uint32_t index);     /* "" for padding */
 VRH_API const char* vrh_obj_material_texture(const vrh_obj* obj, uint32_t index);  /* map_Kd or ""   */
 VRH_API int vrh_obj_free(vrh_obj* obj);

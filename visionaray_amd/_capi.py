@@ -41,6 +41,14 @@ class vrh_plastic(C.Structure):
                 ("cs", C.c_float * 3), ("ks", C.c_float), ("exp", C.c_float)]
 
 
+VRH_MATERIAL_PLASTIC, VRH_MATERIAL_MATTE, VRH_MATERIAL_MIRROR, VRH_MATERIAL_EMISSIVE = 0, 1, 2, 3
+
+
+class vrh_material(C.Structure):
+    """the tagged 64-byte record: the kind word, then the kind's parameters (include/vrh.h)"""
+    _fields_ = [("kind", C.c_uint32), ("params", C.c_float * 15)]
+
+
 class vrh_point_light(C.Structure):
     _fields_ = [("position", C.c_float * 3), ("cl", C.c_float * 3), ("kl", C.c_float), ("constant_att", C.c_float),
                 ("linear_att", C.c_float), ("quadratic_att", C.c_float)]
@@ -166,6 +174,7 @@ SIGNATURES = {
     "vrh_scene_free": (C.c_int, [_vp]),
     "vrh_scene_set_vertex_normals": (C.c_int, [_vp, _vp, _u32]),
     "vrh_shading_create": (C.c_int, [_vp, _vp, _u32, _vp, _u32, C.POINTER(_vp)]),
+    "vrh_shading_create_generic": (C.c_int, [_vp, _vp, _u32, _vp, _u32, C.POINTER(_vp)]),
     "vrh_shading_free": (C.c_int, [_vp]),
     "vrh_hit_mask_create": (C.c_int, [_vp, _vp, _u32, _vp, _u32, _u32, C.POINTER(_vp)]),
     "vrh_hit_mask_free": (C.c_int, [_vp]),
@@ -224,6 +233,7 @@ SIGNATURES = {
     "vrh_obj_load": (C.c_int, [C.c_char_p, C.POINTER(_vp)]),
     "vrh_obj_get_info": (C.c_int, [_vp, C.POINTER(vrh_obj_info)]),
     "vrh_obj_get_data": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "vrh_obj_get_generic_materials": (C.c_int, [_vp, _vp]),
     "vrh_obj_material_name": (C.c_char_p, [_vp, _u32]),
     "vrh_obj_material_texture": (C.c_char_p, [_vp, _u32]),
     "vrh_obj_free": (C.c_int, [_vp]),

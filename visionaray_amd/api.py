@@ -579,17 +579,78 @@ def point_light(position, cl=(1.0, 1.0, 1.0), kl=1.0, constant_att=1.0, linear_a
     return l_
 
 
+# vrh_material: the kind word and the kind's parameters (64 bytes).  params by kind:
+#   plastic  ca[3] ka cd[3] kd cs[3] ks exp      matte     ca[3] ka cd[3] kd
+#   mirror   cr[3] kr ior[3] absorption[3]       emissive  ce[3] ls
+MATERIAL_DTYPE = np.dtype([("kind", "<u4"), ("params", "<f4", 15)])
+MATERIAL_PLASTIC, MATERIAL_MATTE = capi.VRH_MATERIAL_PLASTIC, capi.VRH_MATERIAL_MATTE
+MATERIAL_MIRROR, MATERIAL_EMISSIVE = capi.VRH_MATERIAL_MIRROR, capi.VRH_MATERIAL_EMISSIVE
+
+
+def _material(kind, *params):
+    m = np.zeros((), MATERIAL_DTYPE)
+    m["kind"] = kind
+    flat = np.concatenate([np.atleast_1d(np.asarray(x, np.float32)) for x in params])
+    m["params"][:len(flat)] = flat
+    return m
+
+
+def matte(ca=(0.0, 0.0, 0.0), ka=1.0, cd=(0.8, 0.8, 0.8), kd=1.0):
+    """One matte<float> record (material.h, detail/material/matte.inl: set_ca/ka/cd/kd) of MATERIAL_DTYPE."""
+    return _material(MATERIAL_MATTE, ca, ka, cd, kd)
+
+
+def mirror(cr=(1.0, 1.0, 1.0), kr=1.0, ior=(1.0, 1.0, 1.0), absorption=(0.0, 0.0, 0.0)):
+    """One mirror<float> record (detail/material/mirror.inl: set_cr/kr/ior/absorption; ior and absorption
+    per channel, a scalar is spread as mirror::set_ior(T) does) of MATERIAL_DTYPE."""
+    return _material(MATERIAL_MIRROR, cr, kr, np.broadcast_to(np.float32(ior), 3), np.broadcast_to(np.float32(absorption), 3))
+
+
+def emissive(ce=(1.0, 1.0, 1.0), ls=1.0):
+    """One emissive<float> record (detail/material/emissive.inl: set_ce/ls) of MATERIAL_DTYPE."""
+    return _material(MATERIAL_EMISSIVE, ce, ls)
+
+
+def generic_materials(materials):
+    """A MATERIAL_DTYPE array (a generic_material<plastic, matte, mirror, emissive> list) from a sequence
+    of plastic(...), matte(...), mirror(...) and emissive(...) records or arrays of them; PLASTIC_DTYPE
+    records are lifted (kind plastic, the 13 floats unchanged)."""
+    if isinstance(materials, np.ndarray):
+        materials = [materials]
+    out = []
+    for m in materials:
+        m = np.atleast_1d(np.asarray(m))
+        if m.dtype == MATERIAL_DTYPE:
+            out.append(m)
+        elif m.dtype == PLASTIC_DTYPE:
+            g = np.zeros(len(m), MATERIAL_DTYPE)
+            g["kind"] = MATERIAL_PLASTIC
+            g["params"][:, :13] = np.ascontiguousarray(m).view(np.float32).reshape(len(m), 13)
+            out.append(g)
+        else:
+            raise TypeError("generic_materials: records of MATERIAL_DTYPE or PLASTIC_DTYPE")
+    return np.ascontiguousarray(np.concatenate(out)) if out else np.zeros(0, MATERIAL_DTYPE)
+
+
 class shading:
     """Device materials (plastic, indexed by geom_id) + point lights: the materials / lights
-    arguments of make_kernel_params (kernels.h:357-389), copied to the GPU once."""
+    arguments of make_kernel_params (kernels.h:357-389), copied to the GPU once.
+    generic=True (or generic_shading): `materials` are tagged records (MATERIAL_DTYPE, or anything
+    generic_materials accepts) -- a generic_material model, taken by pathtracing_kernel only."""
 
-    def __init__(self, ctx, materials, lights):
+    def __init__(self, ctx, materials, lights, generic=False):
         self.ctx = ctx
-        self.materials = np.ascontiguousarray(np.atleast_1d(materials), PLASTIC_DTYPE)
+        self.generic = bool(generic)
         self.lights = np.ascontiguousarray(np.atleast_1d(lights), POINT_LIGHT_DTYPE)
         h = C.c_void_p()
-        capi.check("vrh_shading_create", ctx.handle, _p(self.materials), len(self.materials),
-                   _p(self.lights) if len(self.lights) else None, len(self.lights), C.byref(h))
+        if self.generic:
+            self.materials = generic_materials(materials)
+            capi.check("vrh_shading_create_generic", ctx.handle, _p(self.materials), len(self.materials),
+                       _p(self.lights) if len(self.lights) else None, len(self.lights), C.byref(h))
+        else:
+            self.materials = np.ascontiguousarray(np.atleast_1d(materials), PLASTIC_DTYPE)
+            capi.check("vrh_shading_create", ctx.handle, _p(self.materials), len(self.materials),
+                       _p(self.lights) if len(self.lights) else None, len(self.lights), C.byref(h))
         self.handle = h
 
     def close(self):
@@ -604,6 +665,12 @@ class shading:
             pass
 
 
+def generic_shading(ctx, materials, lights=()):
+    """shading(ctx, materials, lights, generic=True): a generic_material<plastic, matte, mirror, emissive>
+    list for pathtracing_kernel."""
+    return shading(ctx, materials, np.zeros(0, POINT_LIGHT_DTYPE) if len(lights) == 0 else lights, generic=True)
+
+
 class model:
     """Scene read from a Wavefront OBJ file: the reference's `model` (src/common/model.h:20-49).
 
@@ -612,6 +679,8 @@ class model:
     geometric_normals  (N, 4) float32, normalize(cross(e1, e2)) -- the per-face normals
     tex_coords         (K, 2) float32, incl. the reference's dummy padding
     materials          PLASTIC_DTYPE (ca = Ka, cd = Kd, cs = Ks, ka = kd = ks = 1, exp = Ns)
+    generic_materials  MATERIAL_DTYPE: emissive (ce = Ke, ls = 1) where length(Ke) > 0, else the plastic
+                       record -- what a model whose material_type is a generic_material gets
     material_names / textures   `usemtl` name and map_Kd path per material ("" for padding)
     bbox               (2, 3) float32 [min, max]
     """
@@ -635,6 +704,9 @@ def load_obj(filename):
         m.materials = np.zeros(info.num_materials, PLASTIC_DTYPE)
         capi.check("vrh_obj_get_data", h, _p(m.primitives), _p(m.geometric_normals), _p(m.shading_normals),
                    _p(m.tex_coords), _p(m.materials))
+        m.generic_materials = np.zeros(info.num_materials, MATERIAL_DTYPE)
+        if info.num_materials:
+            capi.check("vrh_obj_get_generic_materials", h, _p(m.generic_materials))
         m.material_names = [capi.lib().vrh_obj_material_name(h, i).decode() for i in range(info.num_materials)]
         m.textures = [capi.lib().vrh_obj_material_texture(h, i).decode() for i in range(info.num_materials)]
         m.bbox = np.array([list(info.bbox_min), list(info.bbox_max)], np.float32)
@@ -693,9 +765,10 @@ def pathtracing_kernel(bvh, shade, binding=normals_per_face_binding, bg=(0.0, 0.
                        ambient=(1.0, 1.0, 1.0, 1.0), num_bounces=10, epsilon=1e-3, count_tests=False):
     """pathtracing::kernel (detail/pathtracing.inl:29-121) over make_kernel_params(binding, prims, normals,
     materials, lights, num_bounces, epsilon, bg, ambient): a path of up to num_bounces closest-hit rays per
-    pixel, every hit sampling its plastic material with the reference's random_sampler<float> (seeded per
-    pixel and frame number); a path that leaves the scene takes `ambient`, the environment light.  The
-    lights of `shade` are ignored.  Accumulate frames with pixel_sampler.jittered_blend_type."""
+    pixel, every hit sampling its material with the reference's random_sampler<float> (seeded per pixel and
+    frame number): plastic with a shading(...), plastic / matte / mirror / emissive by the record's kind with
+    a generic_shading(...), where a path that hits an emissive surface ends with its radiance.  A path that
+    leaves the scene takes `ambient`, the environment light.  The lights of `shade` are ignored.  Accumulate frames with pixel_sampler.jittered_blend_type."""
     k = simple_kernel(bvh, shade, binding=binding, bg=bg, ambient=ambient, count_tests=count_tests)
     k.desc.kind = capi.VRH_KERNEL_PATHTRACING
     k.desc.num_bounces = num_bounces

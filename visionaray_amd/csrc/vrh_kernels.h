@@ -100,7 +100,7 @@ struct render_params
     dev::hit_mask_params hmask;   // mask intersector (vrh_hit_mask), hmask.mask == null: none
 };
 
-// register budget (waves / SIMD) of the path-tracing instances (render_unified_kernel<..., EPI 4>)
+// register budget (waves / SIMD) of the path-tracing instances (render_unified_kernel<..., EPI 4 / 5>)
 constexpr int PATH_OCC = 5;
 
 constexpr int COUNTERS_FRAME = 208;     // u64 words reset before every frame
@@ -130,7 +130,8 @@ struct launch_config
                        // 2: step loop over a BVH list (render_unified_kernel<..., LIST>),
                        // 3: step loop, frames in flight (render_unified_kernel<..., BATCH>: same code),
                        // 6: a pixel-sampler pass (render_unified_kernel<..., SAMPLED>)
-    int epi;           // primary epilogue: 0 plain, 1 VRH_KERNEL_SIMPLE, 2 VRH_KERNEL_MULTI_HIT, 3 VRH_KERNEL_WHITTED, 4 VRH_KERNEL_PATHTRACING (triangles)
+    int epi;           // primary epilogue: 0 plain, 1 VRH_KERNEL_SIMPLE, 2 VRH_KERNEL_MULTI_HIT, 3 VRH_KERNEL_WHITTED, 4 VRH_KERNEL_PATHTRACING (triangles),
+                       // 5 VRH_KERNEL_PATHTRACING with a generic shading (tagged material records)
     int max_hits;      // MULTI_HIT: N (LDS hit lists)
     bool spill;        // the traversal stack continues in a global overflow block (render_unified_kernel<..., SPILL>)
     bool share;        // AO tail sharing (render_unified_kernel<..., SHARE>): one-frame AO launches at 5 waves / SIMD

@@ -580,7 +580,8 @@ __device__ __forceinline__ uint32_t kernarg_root()
 // shadow and reflection rays one after the other before it takes the next pixel), 4
 // pathtracing::kernel (the lane traces its pixel's path, one closest-hit ray per bounce, the
 // sampler seeded per pixel from the camera's full image size: shards and scissor boxes draw the
-// same numbers).
+// same numbers), 5 the same loop over tagged material records (generic_material: plastic, matte,
+// mirror, emissive by the hit's record; vrh_shade.h pt_bounce_generic).
 // LIST: the scene is a list of BVHs (vrh_scene_list_create), traversed one after the other per ray
 // and merged as traverse_linear.inl:76-141 does (list_next); EPI 0 only.
 // BATCH: the same code, instantiated separately for launches of several frames (vrh_render_batch,
@@ -671,7 +672,7 @@ __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params 
                                 w.color = mk3(0.0f, 0.0f, 0.0f); w.thr = 1.0f; w.depth = 0; w.shadow = 0;
                                 max_t = FMAX; any = false; quad = false;
                             }
-                            if constexpr (EPI == 4)
+                            if constexpr (EPI == 4 || EPI == 5)
                             {
                                 pt.dst = mk3(1.0f, 1.0f, 1.0f); pt.bounce = 0;
                                 pt.x = minstd_seed(pixel_seed(x, y, P.width, P.height, P.frame_num + fr));
@@ -691,7 +692,7 @@ __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params 
             }
             const bool busy = mode != IDLE;
             using ML = typename std::conditional<EPI == 2, mh_list, void>::type;
-            constexpr bool UV = EPI == 1 || EPI == 3 || EPI == 4;
+            constexpr bool UV = EPI == 1 || EPI == 3 || EPI == 4 || EPI == 5;
             const float mt = EPI == 3 ? max_t : FMAX;
             const bool an = EPI == 3 ? any : false;
             if (mode != IDLE)
@@ -776,7 +777,7 @@ __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params 
                         }
                     }
                 }
-                else if constexpr (EPI == 4)
+                else if constexpr (EPI == 4 || EPI == 5)
                 {
                     if (rc != 0)
                     {
@@ -800,13 +801,22 @@ __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params 
                         {
                             // the last bounce's sample cannot reach the image: a path still alive after it
                             // is set to 0, one killed by pdf <= 0 is 0 too
+                            // (EPI 5: unless the surface is emissive, whose path ended keeping its radiance)
                             lit = P.num_bounces != 0u;
-                            pt.dst = mk3(0.0f, 0.0f, 0.0f);
+                            if constexpr (EPI == 5)
+                            {
+                                if (lit) pt_last_generic(P.shade, P.prims, pt, hx.li);
+                            }
+                            else
+                                pt.dst = mk3(0.0f, 0.0f, 0.0f);
                         }
                         else
                         {
                             lit = true;
-                            done = !pt_bounce(P.shade, P.prims, P.normals, pt, r, best_t, best_prim, hx, P.eps);
+                            if constexpr (EPI == 5)
+                                done = !pt_bounce_generic(P.shade, P.prims, P.normals, pt, r, best_t, best_prim, hx, P.eps);
+                            else
+                                done = !pt_bounce(P.shade, P.prims, P.normals, pt, r, best_t, best_prim, hx, P.eps);
                         }
                         if (!done)
                         {
@@ -1239,13 +1249,14 @@ static kernel_fn pick_shade(bool count, int epi)
 
 // pathtracing::kernel (EPI 4, triangles): one frame, frames in flight (BATCH) and a pixel-sampler pass
 // (SAMPLED), at the default register budget and uncapped (occ 1); test counting on one-frame launches
-template <int OCC>
+// EPI 5: the same set for a generic shading (tagged material records)
+template <int OCC, int EPI = 4>
 static kernel_fn pick_path(bool count, int sched)
 {
-    if (sched == 6) return dev::render_unified_kernel<dev::KIND_TRI, false, false, OCC, 4, false, false, false, true>;
-    if (sched == 3) return dev::render_unified_kernel<dev::KIND_TRI, false, false, OCC, 4, false, true>;
-    if (count) return OCC == 1 ? dev::render_unified_kernel<dev::KIND_TRI, false, true, 1, 4> : nullptr;
-    return dev::render_unified_kernel<dev::KIND_TRI, false, false, OCC, 4>;
+    if (sched == 6) return dev::render_unified_kernel<dev::KIND_TRI, false, false, OCC, EPI, false, false, false, true>;
+    if (sched == 3) return dev::render_unified_kernel<dev::KIND_TRI, false, false, OCC, EPI, false, true>;
+    if (count) return OCC == 1 ? dev::render_unified_kernel<dev::KIND_TRI, false, true, 1, EPI> : nullptr;
+    return dev::render_unified_kernel<dev::KIND_TRI, false, false, OCC, EPI>;
 }
 
 template <int KIND>
@@ -1285,6 +1296,7 @@ static kernel_fn select_variant(const launch_config& c)
     if (c.share)
         if (kernel_fn f = c.kind == dev::KIND_TRI ? pick_share<dev::KIND_TRI>(c) : pick_share<dev::KIND_SPHERE>(c)) return f;
     if (c.epi == 4) return c.occ == 1 ? pick_path<1>(c.count, c.sched) : pick_path<PATH_OCC>(c.count, c.sched);
+    if (c.epi == 5) return c.occ == 1 ? pick_path<1, 5>(c.count, c.sched) : pick_path<PATH_OCC, 5>(c.count, c.sched);
     if (c.epi) return c.occ == 8 ? pick_shade<8>(c.count, c.epi) : c.occ == 6 ? pick_shade<6>(c.count, c.epi)
                     : c.occ == 5 ? pick_shade<5>(c.count, c.epi) : pick_shade<1>(c.count, c.epi);
     if (c.spill)

@@ -339,6 +339,7 @@ struct obj_model
     std::vector<v3> shading_normals, geometric_normals;
     std::vector<float> tex_coords;          // 2 per entry
     std::vector<vrh_plastic> materials;
+    std::vector<v3> emission;               // per material: Ke (0 for padding), vrh_obj_get_generic_materials
     std::vector<std::string> material_names, textures;   // per material: usemtl name, map_Kd
     v3 bbox_min, bbox_max;
     uint32_t degenerate = 0, unknown_materials = 0, missing_files = 0;
@@ -465,6 +466,7 @@ int load_obj(const std::string& filename, obj_model& m, std::string& err)
                     p.cs[0] = e.ks.x; p.cs[1] = e.ks.y; p.cs[2] = e.ks.z; p.ks = 1.0f;
                     p.exp = e.ns;
                     m.materials.push_back(p);
+                    m.emission.push_back(e.ke);
                     m.material_names.push_back(name);
                     m.textures.push_back(e.map_kd);
                 }
@@ -577,6 +579,7 @@ int load_obj(const std::string& filename, obj_model& m, std::string& err)
     for (size_t i = m.materials.size(); i <= geom_id; ++i)
     {
         m.materials.push_back(default_material());
+        m.emission.push_back(v3{ 0.0f, 0.0f, 0.0f });
         m.material_names.emplace_back();
         m.textures.emplace_back();
     }
@@ -661,6 +664,31 @@ extern "C" VRH_API int vrh_obj_get_data(const vrh_obj* m, void* triangles, float
         std::memcpy(tex_coords, m->tex_coords.data(), m->tex_coords.size() * sizeof(float));
     if (materials && !m->materials.empty())
         std::memcpy(materials, m->materials.data(), m->materials.size() * sizeof(vrh_plastic));
+    return VRH_OK;
+}
+
+// add_material(generic_material<Ts...>, cont, m), obj_loader.cpp:274-296
+extern "C" VRH_API int vrh_obj_get_generic_materials(const vrh_obj* m, vrh_material* materials)
+{
+    if (!m || !materials) { set_error("vrh_obj_get_generic_materials: null argument"); return VRH_ERR_INVALID; }
+    for (size_t i = 0; i < m->materials.size(); ++i)
+    {
+        vrh_material g;
+        std::memset(&g, 0, sizeof(g));
+        const v3 ke = m->emission[i];
+        if (std::sqrt(dot(ke, ke)) > 0.0f)
+        {
+            g.kind = VRH_MATERIAL_EMISSIVE;
+            g.u.emissive.ce[0] = ke.x; g.u.emissive.ce[1] = ke.y; g.u.emissive.ce[2] = ke.z;
+            g.u.emissive.ls = 1.0f;
+        }
+        else
+        {
+            g.kind = VRH_MATERIAL_PLASTIC;
+            g.u.plastic = m->materials[i];
+        }
+        materials[i] = g;
+    }
     return VRH_OK;
 }
 

@@ -93,7 +93,8 @@ struct vrh_scene
 struct vrh_shading
 {
     vrh_ctx* ctx = nullptr;
-    vrh::dev::plastic_t* materials = nullptr;
+    vrh::dev::plastic_t* materials = nullptr;      // plastic records (vrh_shading_create), or
+    vrh::dev::material_t* gmaterials = nullptr;    // tagged records (vrh_shading_create_generic): path tracer only
     vrh::dev::point_light_t* lights = nullptr;
     uint32_t num_materials = 0, num_lights = 0;
 };

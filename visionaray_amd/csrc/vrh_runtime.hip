@@ -743,6 +743,44 @@ VRH_API int vrh_shading_create(vrh_ctx* ctx, const vrh_plastic* materials, uint3
     return VRH_OK;
 }
 
+VRH_API int vrh_shading_create_generic(vrh_ctx* ctx, const vrh_material* materials, uint32_t num_materials,
+                                       const vrh_point_light* lights, uint32_t num_lights, vrh_shading** out)
+{
+    static_assert(sizeof(vrh_material) == 64 && sizeof(vrh_material) == sizeof(dev::material_t), "material layout");
+    static_assert(offsetof(vrh_material, u) == 4 && offsetof(dev::material_t, p) == 4, "material layout");
+    static_assert(int(VRH_MATERIAL_PLASTIC) == int(dev::MAT_PLASTIC) && int(VRH_MATERIAL_MATTE) == int(dev::MAT_MATTE)
+                  && int(VRH_MATERIAL_MIRROR) == int(dev::MAT_MIRROR) && int(VRH_MATERIAL_EMISSIVE) == int(dev::MAT_EMISSIVE),
+                  "material kinds");
+    VRH_CHECK(ctx && out && materials && num_materials > 0, "vrh_shading_create_generic: need at least one material");
+    VRH_CHECK(num_lights == 0 || lights, "vrh_shading_create_generic: null lights");
+    *out = nullptr;
+    for (uint32_t i = 0; i < num_materials; ++i)
+        VRH_CHECK(materials[i].kind <= VRH_MATERIAL_EMISSIVE,
+                  "vrh_shading_create_generic: material " + std::to_string(i) + " has unknown kind " + std::to_string(materials[i].kind));
+    int rc = select_device(ctx);
+    if (rc) return rc;
+    auto* sh = new (std::nothrow) vrh_shading;
+    if (!sh) { set_error("host allocation failed"); return VRH_ERR_OOM; }
+    sh->ctx = ctx;
+    sh->num_materials = num_materials;
+    sh->num_lights = num_lights;
+    hipError_t e = hipMalloc(&sh->gmaterials, sizeof(vrh_material) * num_materials);
+    if (e == hipSuccess) e = hipMemcpy(sh->gmaterials, materials, sizeof(vrh_material) * num_materials, hipMemcpyHostToDevice);
+    if (e == hipSuccess && num_lights)
+    {
+        e = hipMalloc(&sh->lights, sizeof(vrh_point_light) * num_lights);
+        if (e == hipSuccess) e = hipMemcpy(sh->lights, lights, sizeof(vrh_point_light) * num_lights, hipMemcpyHostToDevice);
+    }
+    if (e != hipSuccess)
+    {
+        set_error(std::string("vrh_shading_create_generic: ") + hipGetErrorString(e));
+        vrh_shading_free(sh);
+        return e == hipErrorOutOfMemory ? VRH_ERR_OOM : VRH_ERR_HIP;
+    }
+    *out = sh;
+    return VRH_OK;
+}
+
 VRH_API int vrh_hit_mask_create(vrh_ctx* ctx, const float* tex_coords, uint32_t num_tex_coords,
                                 const uint8_t* mask, uint32_t mask_width, uint32_t mask_height, vrh_hit_mask** out)
 {
@@ -789,6 +827,7 @@ VRH_API int vrh_shading_free(vrh_shading* sh)
     if (!sh) return VRH_OK;
     if (sh->ctx) (void)hipSetDevice(sh->ctx->device);
     if (sh->materials) (void)hipFree(sh->materials);
+    if (sh->gmaterials) (void)hipFree(sh->gmaterials);
     if (sh->lights) (void)hipFree(sh->lights);
     delete sh;
     return VRH_OK;
@@ -1122,6 +1161,11 @@ int render_batch_impl(vrh_ctx* ctx, const vrh_scene* sc, vrh_rt* rt, const vrh_c
     if (shade)
     {
         VRH_CHECK(k->shading, "vrh_render: the shading kernels need a vrh_shading (materials, lights)");
+        if (k->shading->gmaterials && !path)
+        {
+            set_error("vrh_render: a generic shading (vrh_shading_create_generic) is taken by VRH_KERNEL_PATHTRACING only");
+            return VRH_ERR_UNSUPPORTED;
+        }
         if (sc->info.prim_kind != VRH_PRIM_TRI64) { set_error("vrh_render: the shading kernels support triangles"); return VRH_ERR_UNSUPPORTED; }
         if (list) { set_error("vrh_render: the shading kernels take a single BVH (scene lists: primary and AO kernels)"); return VRH_ERR_UNSUPPORTED; }
         VRH_CHECK(k->shading->num_materials > sc->info.max_geom_id, "vrh_render: a geom_id has no material");
@@ -1175,7 +1219,7 @@ int render_batch_impl(vrh_ctx* ctx, const vrh_scene* sc, vrh_rt* rt, const vrh_c
     lc.block = ctx->opt_block ? ctx->opt_block : ao_share ? 256 : 64;
     lc.share = ao_share;
     lc.stack_cap = int(cap);
-    lc.epi = path ? 4 : whitted ? 3 : multi ? 2 : shade ? 1 : 0;
+    lc.epi = path ? (k->shading->gmaterials ? 5 : 4) : whitted ? 3 : multi ? 2 : shade ? 1 : 0;
     lc.max_hits = multi ? int(k->max_hits) : 0;
     // every kernel runs the step loop (the round-1 item loop for sphere primary visibility measured
     // 6-9 % slower than the step loop with its round-2 defaults, profiles/r02_ab/ab18_sphere_schedule.log,
@@ -1199,6 +1243,8 @@ int render_batch_impl(vrh_ctx* ctx, const vrh_scene* sc, vrh_rt* rt, const vrh_c
     // fit 94 (one frame, frames in flight) / 96 (sampler pass) VGPRs with no VGPR spill and no scratch
     // (-Rpass-analysis=kernel-resource-usage), so 5 is the default -- not compared on the GPU against 4;
     // waves_per_simd 1 and the counting variant (163 VGPRs) run uncapped.
+    // The instances over tagged materials (EPI 5, a generic shading): 96 / 96 / 96 VGPRs capped at PATH_OCC, no
+    // VGPR spill and no scratch either; uncapped 110 (4 waves/SIMD), the counting variant 165.
     // AO on the step loop (round 5, the lean lane state: no VGPR spill or scratch at 80 VGPRs, also in
     // the overflow-stack instances): 6 waves/SIMD, the LDS stack shrunk (below) to 16 entries so that 24
     // waves fit a CU, the rest in the overflow block -- hf1M +4.8 %, hf10M +8.7 % over 5 waves
@@ -1281,7 +1327,7 @@ int render_batch_impl(vrh_ctx* ctx, const vrh_scene* sc, vrh_rt* rt, const vrh_c
     // +1.8 % hf10M at 20 frames per launch (profiles/r02_ab/ab20_refill.log); simple::kernel and
     // whitted once 8 are: +1-2.5 % / +1 % (profiles/r02_ab/shade_refill.jsonl); one-frame primary
     // launches and multi_hit keep 1
-    const uint32_t refill_shade = (lc.epi == 1 || lc.epi == 3 || lc.epi == 4) ? 8u : 1u;
+    const uint32_t refill_shade = (lc.epi == 1 || lc.epi == 3 || lc.epi == 4 || lc.epi == 5) ? 8u : 1u;
     p.refill_min_primary = ctx->opt_refill ? uint32_t(ctx->opt_refill)
                          : (primary_step && num_frames > 1) ? 16u : lc.epi ? refill_shade : 1u;
     // primary visibility caps a lane's descent at 8 inner visits per step; at 8 waves / SIMD (round 5,
@@ -1366,7 +1412,8 @@ int render_batch_impl(vrh_ctx* ctx, const vrh_scene* sc, vrh_rt* rt, const vrh_c
     p.cluster = ctx->opt_cluster ? uint32_t(ctx->opt_cluster) : 8u;
     if (shade)
     {
-        p.shade.materials = k->shading->materials;
+        if (k->shading->gmaterials) p.shade.gmaterials = k->shading->gmaterials;
+        else p.shade.materials = k->shading->materials;
         p.shade.lights = k->shading->lights;
         p.shade.num_lights = k->shading->num_lights;
         p.shade.per_vertex = k->normal_binding == VRH_NORMALS_PER_VERTEX ? 1u : 0u;

@@ -20,9 +20,19 @@ namespace dev {
 struct plastic_t { float ca[3]; float ka; float cd[3]; float kd; float cs[3]; float ks; float exp; };
 struct point_light_t { float position[3]; float cl[3]; float kl; float constant_att, linear_att, quadratic_att; };
 
+// device copy of vrh_material (include/vrh.h): the kind word and the kind's parameters, fetched as four
+// 16-byte loads.  p[]: plastic ca[3] ka cd[3] kd cs[3] ks exp; matte ca[3] ka cd[3] kd (the plastic
+// record's first eight words); mirror cr[3] kr ior[3] absorption[3]; emissive ce[3] ls
+struct __attribute__((aligned(16))) material_t { uint32_t kind; float p[15]; };
+constexpr uint32_t MAT_PLASTIC = 0, MAT_MATTE = 1, MAT_MIRROR = 2, MAT_EMISSIVE = 3;
+
 struct shade_params
 {
-    const plastic_t* materials;
+    union
+    {
+        const plastic_t* materials;
+        const material_t* gmaterials;   // a generic shading (vrh_shading_create_generic): EPI 5 only
+    };
     const point_light_t* lights;
     uint32_t num_lights;
     uint32_t per_vertex;          // normals_per_vertex_binding
@@ -37,6 +47,8 @@ struct surface_t { f3 gn, sn; plastic_t m; uint32_t mi; };
 
 // get_surface (get_surface.h:336-376, 576-592) for a triangle hit: normals by binding, material by
 // the primitive's geom_id
+// (GENERIC: the material is left to the caller, which fetches the tagged record by sf.mi)
+template <bool GENERIC = false>
 __device__ inline surface_t get_surface(const shade_params& S, const float4* __restrict__ prims,
                                         const float4* __restrict__ normals, uint32_t prim_id, uint32_t li,
                                         float u, float v)
@@ -45,7 +57,7 @@ __device__ inline surface_t get_surface(const shade_params& S, const float4* __r
     const float4* q = prims + 3u * li;
     const float4 qb = q[1], qc = q[2];
     sf.mi = __float_as_uint(qc.z);
-    sf.m = S.materials[sf.mi];
+    if constexpr (!GENERIC) sf.m = S.materials[sf.mi];
     if (!S.per_vertex)
     {
         const float4 nn = normals[prim_id];                            // get_normal.h:26-37
@@ -266,6 +278,154 @@ __device__ inline bool pt_bounce(const shade_params& S, const float4* __restrict
         const f3 schlick = spec + mk3(1.0f - spec.x, 1.0f - spec.y, 1.0f - spec.z) * p5;
         const float nfactor = (m.exp + 2.0f) / (8.0f * PI);
         src = (schlick * nfactor) * __builtin_powf(hdotn, m.exp);
+    }
+    if (pdf <= 0.0f)
+    {
+        w.dst = mk3(0.0f, 0.0f, 0.0f);
+        return false;
+    }
+    src = src * (dot(n, wi) / pdf);
+    w.dst = mk3(w.dst.x * src.x, w.dst.y * src.y, w.dst.z * src.z);
+    const f3 pos = r.ori + r.dir * t;
+    r = make_ray(pos + wi * eps, wi);
+    return true;
+}
+
+// The same bounce for a generic_material<plastic, matte, mirror, emissive> (detail/generic_material.inl
+// sample_visitor; pathtracing.inl:73-113): the hit's record says which material samples.  The kind is
+// per lane, so the bodies diverge inside a wave; the lane state between rays is pt_lane as above.
+//   plastic   the code of pt_bounce: u, then two draws (lambertian second argument first, blinn u1 u2)
+//   matte     lambertian::sample_f (brdf.h:44-62) with NO selection draw: two draws, second argument first
+//   mirror    specular_reflection::sample_f (brdf.h:188-209): wi = reflect(wo, n), pdf = 1, no draws,
+//             src = fresnel_reflectance(conductor, ior, absorption, |dot(n, wo)|) * (cr * kr) / |dot(n, wi)|
+//             (fresnel.h:18-35), then * dot(n, wi) / pdf like every sampled direction
+//   emissive  emissive::sample (emissive.inl:29-40, 78-82): pdf = 1, src = ce * ls, no draws; src is NOT
+//             scaled by dot / pdf, dst *= src and the path ends KEEPING dst (pathtracing.inl:94-101; the
+//             final select zeroes only paths still alive)
+// Returns false when the path ends (emissive: dst is the pixel's radiance; pdf <= 0: dst = 0).
+// Every body loads the 16-byte quarters of the record it reads where it reads them (the kind word comes
+// with the first), so no lane holds all sixteen words across the sampling code.
+// The last iteration of the loop (bounce == num_bounces - 1) on a hit: its sample reaches the image only
+// through an emissive surface (dst *= ce * ls, the path ended); any other path is still alive after the
+// loop, or was killed by pdf <= 0, and is 0 either way
+__device__ inline void pt_last_generic(const shade_params& S, const float4* __restrict__ prims, pt_lane& w, uint32_t li)
+{
+    const uint32_t mi = __float_as_uint(prims[3u * li + 2u].z);
+    const float4* mp = reinterpret_cast<const float4*>(S.gmaterials + mi);
+    const float4 q0 = mp[0];
+    f3 src = mk3(0.0f, 0.0f, 0.0f);
+    if (__float_as_uint(q0.x) == MAT_EMISSIVE)
+    {
+        const float ls = mp[1].x;
+        src = mk3(q0.y, q0.z, q0.w) * ls;
+        w.dst = mk3(w.dst.x * src.x, w.dst.y * src.y, w.dst.z * src.z);
+    }
+    else
+        w.dst = src;
+}
+
+__device__ inline bool pt_bounce_generic(const shade_params& S, const float4* __restrict__ prims,
+                                         const float4* __restrict__ normals, pt_lane& w, ray_t& r, float t,
+                                         uint32_t prim_id, const hit_extra& hx, float eps)
+{
+    constexpr float PI = 3.14159265358979323846264338328e+00f;      // math.h:240-242 constants
+    constexpr float TWO_PI = 6.28318530717958647692528676656e+00f;
+    constexpr float INV_PI = 3.18309886183790691216444201928e-01f;
+    const surface_t sf = get_surface<true>(S, prims, normals, prim_id, hx.li, hx.u, hx.v);
+    // words of the record: q0 = kind p0 p1 p2, q1 = p3..p6, q2 = p7..p10, q3 = p11..p14 (material_t)
+    const float4* mp = reinterpret_cast<const float4*>(S.gmaterials + sf.mi);
+    const uint32_t kind = __float_as_uint(mp[0].x);
+    if (kind == MAT_EMISSIVE)
+    {
+        const float4 q0 = mp[0];
+        const f3 src = mk3(q0.y, q0.z, q0.w) * mp[1].x;               // ce_ * ls_
+        w.dst = mk3(w.dst.x * src.x, w.dst.y * src.y, w.dst.z * src.z);
+        return false;
+    }
+    const f3 wo = neg(r.dir);
+    const f3 n = dot(sf.gn, wo) < 0.0f ? neg(sf.sn) : sf.sn;         // faceforward, vector.inl:674-681
+    f3 wi, src;
+    float pdf;
+    if (kind == MAT_MIRROR)
+    {
+        const float4 q0 = mp[0], q1 = mp[1], q2 = mp[2];
+        const float ior[3] = { q1.y, q1.z, q1.w }, absorption[3] = { q2.x, q2.y, q2.z };
+        const float d2 = 2.0f * dot(n, wo);                           // reflect(wo, n), vector.inl:683-689
+        wi = mk3(d2 * n.x, d2 * n.y, d2 * n.z) - wo;
+        pdf = 1.0f;
+        const float cosi = fabsf(dot(n, wo));
+        float fr[3];
+        for (int c = 0; c < 3; ++c)
+        {
+            // fresnel_reflectance(conductor_tag, eta, k, cosi), fresnel.h:18-35
+            const float eta = ior[c], k = absorption[c];
+            const float a = eta * eta + k * k;
+            const float b = (2.0f * eta) * cosi;
+            const float rs2 = ((a - b) + cosi * cosi) / ((a + b) + cosi * cosi);
+            const float rp2 = (((a * cosi) * cosi - b) + 1.0f) / (((a * cosi) * cosi + b) + 1.0f);
+            fr[c] = (rs2 + rp2) / 2.0f;
+        }
+        const f3 crkr = mk3(q0.y, q0.z, q0.w) * q1.x;
+        const float adot = fabsf(dot(n, wi));
+        src = mk3((fr[0] * crkr.x) / adot, (fr[1] * crkr.y) / adot, (fr[2] * crkr.z) / adot);
+    }
+    else
+    {
+        bool diffuse = true;                                          // matte: lambertian, no selection draw
+        if (kind == MAT_PLASTIC)
+        {
+            // plastic::sample_impl (plastic.inl:186-230), mean_value (spectrum.inl:268-271): hadd / 3
+            const float4 q1 = mp[1], q2 = mp[2];
+            float prob_diff = (((q1.y + q1.z) + q1.w) / 3.0f) * q2.x;
+            float prob_spec = (((q2.y + q2.z) + q2.w) / 3.0f) * mp[3].x;
+            const bool all_zero = prob_diff == 0.0f && prob_spec == 0.0f;
+            prob_diff = all_zero ? 0.5f : prob_diff;
+            prob_spec = all_zero ? 0.5f : prob_spec;
+            prob_diff = prob_diff / (prob_diff + prob_spec);
+            const float u = minstd_next(w.x);
+            diffuse = u < prob_diff;
+        }
+        f3 bu, bv;
+        pt_basis(n, bu, bv);
+        if (diffuse)
+        {
+            // lambertian::sample_f (brdf.h:44-62), cosine_sample_hemisphere (sampling.h:61-71)
+            const float u2 = minstd_next(w.x);
+            const float u1 = minstd_next(w.x);
+            const float rr = __builtin_sqrtf(u1);
+            const float theta = TWO_PI * u2;
+            const float sx = rr * libm::cosf(theta);
+            const float sy = rr * libm::sinf(theta);
+            const float sz = __builtin_sqrtf(tmax(0.0f, 1.0f - u1));
+            wi = normalize((sx * bu + sy * bv) + sz * n);
+            pdf = dot(n, wi) * INV_PI;
+            const float4 q1 = mp[1];
+            src = (mk3(q1.y, q1.z, q1.w) * mp[2].x) * INV_PI;
+        }
+        else
+        {
+            // blinn::sample_f (brdf.h:128-155), returning blinn::f (brdf.h:114-126)
+            const float4 q2 = mp[2], q3 = mp[3];
+            const float ex = q3.y;
+            const float u1 = minstd_next(w.x);
+            const float u2 = minstd_next(w.x);
+            const float costheta = __builtin_powf(u1, 1.0f / (ex + 1.0f));
+            const float sintheta = __builtin_sqrtf(tmax(0.0f, 1.0f - costheta * costheta));
+            const float phi = u2 * TWO_PI;
+            const f3 h = normalize(((sintheta * libm::cosf(phi)) * bu + (sintheta * libm::sinf(phi)) * bv) + costheta * n);
+            const float d2 = 2.0f * dot(h, wo);                       // reflect(wo, h), vector.inl:683-689
+            wi = mk3(d2 * h.x, d2 * h.y, d2 * h.z) - wo;
+            const float vdoth = dot(wo, h);
+            pdf = ((ex + 1.0f) * __builtin_powf(costheta, ex)) / (((2.0f * PI) * 4.0f) * vdoth);
+            const f3 h2 = normalize(wo + wi);
+            const float hdotn = tmax(0.0f, dot(h2, n));
+            const f3 spec = mk3(q2.y, q2.z, q2.w) * q3.x;
+            const float sat = tmax(0.0f, tmin(dot(wi, h2), 1.0f));
+            const float p5 = __builtin_powf(1.0f - sat, 5.0f);
+            const f3 schlick = spec + mk3(1.0f - spec.x, 1.0f - spec.y, 1.0f - spec.z) * p5;
+            const float nfactor = (ex + 2.0f) / (8.0f * PI);
+            src = (schlick * nfactor) * __builtin_powf(hdotn, ex);
+        }
     }
     if (pdf <= 0.0f)
     {
