@@ -78,7 +78,7 @@ def test_ao_share_option_range(ctx):
 def test_ao_share_keeps_block_size_where_no_share_instance(ctx, scene):
     """Sharing exists only for one-frame AO launches at 5 waves / SIMD: a batched AO launch or a primary
     launch with the option set runs the plain instance at its usual 64-thread block, and a one-frame AO
-    launch runs 4-wave blocks (the kernel selection decides, vrh_kernels.hip render_share_available)."""
+    launch runs 4-wave blocks (the instance set decides, vrh_launch.h instance_exists)."""
     dev, cam, _ = scene
     basis = cam.basis(W, H)
     ctx.set_option("ao_share", 1)

@@ -2,6 +2,7 @@
 #pragma once
 
 #include "../../include/vrh.h"
+#include "vrh_launch.h"
 #include "vrh_shade.h"
 
 #include <hip/hip_runtime.h>
@@ -23,7 +24,7 @@ struct render_params
     const float4* prims;      // leaf-ordered primitives (3 float4 tri, 2 float4 sphere)
     const float4* normals;    // per prim_id
     uint32_t root;            // root link (pair 0, or LEAF_BIT|0 for a single-leaf tree) = roots[0]
-    uint32_t roots[MAX_LIST]; // scene list (launch_config::sched 2): root link of each BVH
+    uint32_t roots[MAX_LIST]; // scene list (instance_key::list): root link of each BVH
     uint32_t num_roots;
     uint32_t step_limit;      // per-ray traversal step bound (nodes + primitives)
     uint32_t stack_cap;       // LDS stack entries per lane
@@ -100,9 +101,6 @@ struct render_params
     dev::hit_mask_params hmask;   // mask intersector (vrh_hit_mask), hmask.mask == null: none
 };
 
-// register budget (waves / SIMD) of the path-tracing instances (render_unified_kernel<..., EPI 4 / 5>)
-constexpr int PATH_OCC = 5;
-
 constexpr int COUNTERS_FRAME = 208;     // u64 words reset before every frame
 constexpr int COUNTERS_LINES = 80;      // [80] L1 128-B lines, [81] wave-level vector-memory instructions, [82] 16-B requests,
                                         // [83] 4-lane-group accesses, [84] ideal-grouping accesses (counting variant)
@@ -118,30 +116,10 @@ constexpr int VRH_MAX_FRAME_LANES = 4;  // asynchronous frames: frame lanes of a
 #endif
 constexpr int COUNTER_BLOCKS = 1 + VRH_MAX_FRAME_LANES;   // per context: frames on its stream + one per frame lane
 
-struct launch_config
-{
-    int kind;          // 0 triangles, 1 spheres
-    bool ao;
-    bool count;        // VRH_KERNEL_COUNT_TESTS variant
-    int block;         // threads per block (multiple of 64)
-    int stack_cap;     // LDS stack entries per lane
-    int occ;           // register budget: min waves per SIMD (1, 6 or 8)
-    int sched;         // 0: step loop (render_unified_kernel),
-                       // 2: step loop over a BVH list (render_unified_kernel<..., LIST>),
-                       // 3: step loop, frames in flight (render_unified_kernel<..., BATCH>: same code),
-                       // 6: a pixel-sampler pass (render_unified_kernel<..., SAMPLED>)
-    int epi;           // primary epilogue: 0 plain, 1 VRH_KERNEL_SIMPLE, 2 VRH_KERNEL_MULTI_HIT, 3 VRH_KERNEL_WHITTED, 4 VRH_KERNEL_PATHTRACING (triangles),
-                       // 5 VRH_KERNEL_PATHTRACING with a generic shading (tagged material records)
-    int max_hits;      // MULTI_HIT: N (LDS hit lists)
-    bool spill;        // the traversal stack continues in a global overflow block (render_unified_kernel<..., SPILL>)
-    bool share;        // AO tail sharing (render_unified_kernel<..., SHARE>): one-frame AO launches at 5 waves / SIMD
-};
-
 size_t render_lds_bytes(const launch_config& c);
+// hipErrorInvalidDeviceFunction for a key without an instance (vrh_launch.h instance_exists)
 hipError_t launch_render(const render_params& p, const launch_config& c, int grid, hipStream_t s);
 int render_blocks_per_cu(const launch_config& c);
-bool render_spill_available(const launch_config& c);   // an overflow-stack instance exists for c
-bool render_share_available(const launch_config& c);   // an AO tail-sharing instance exists for c
 struct unshard_params
 {
     uint32_t width, height, count, rows_per_shard;

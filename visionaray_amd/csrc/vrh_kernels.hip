@@ -19,6 +19,7 @@
 #include <map>
 #include <mutex>
 #include <tuple>
+#include <utility>
 #include "vrh_kernels.h"
 #include "vrh_plan.h"
 
@@ -1205,131 +1206,39 @@ __global__ void pack_code_kernel(const uint32_t* __restrict__ pid, const uint8_t
 
 using kernel_fn = void (*)(render_params);
 
-template <int KIND, int OCC>
-static kernel_fn pick_occ(bool ao, bool count, int sched)
+// the instance of key_at(I), named here and nowhere else: null where instance_exists says there is none
+template <size_t I>
+static kernel_fn instance_at()
 {
-    if (sched == 2)   // BVH list (step loop), at the default register budgets
-    {
-        if (!ao) return count ? dev::render_unified_kernel<KIND, false, true, 6, 0, true> : dev::render_unified_kernel<KIND, false, false, 6, 0, true>;
-        return count ? dev::render_unified_kernel<KIND, true, true, 5, 0, true> : dev::render_unified_kernel<KIND, true, false, 5, 0, true>;
-    }
-    if (sched == 6)   // a pixel-sampler pass (vrh_render_sampled): jittered / offset rays, blended colour
-    {
-        if constexpr (OCC == 5 || OCC == 6)
-            return ao ? dev::render_unified_kernel<KIND, true, false, OCC, 0, false, false, false, true>
-                      : dev::render_unified_kernel<KIND, false, false, OCC, 0, false, false, false, true>;
+    constexpr instance_key k = key_at(I);
+    if constexpr (instance_exists(k))
+        return dev::render_unified_kernel<k.kind, k.ao, k.count, k.occ, int(k.epi), k.list, k.batch, k.spill, k.sampled, k.share>;
+    else
         return nullptr;
-    }
-    if (sched == 3)   // frames in flight (a distinct symbol for profiles), step loop
-        return ao ? dev::render_unified_kernel<KIND, true, false, OCC, 0, false, true>
-                  : dev::render_unified_kernel<KIND, false, false, OCC, 0, false, true>;
-    if (sched == 4)   // sched 0 / 3 with the stack overflow block (launch_config::spill)
-        return ao ? dev::render_unified_kernel<KIND, true, false, OCC, 0, false, false, true>
-                  : dev::render_unified_kernel<KIND, false, false, OCC, 0, false, false, true>;
-    if (sched == 5)
-        return ao ? dev::render_unified_kernel<KIND, true, false, OCC, 0, false, true, true>
-                  : dev::render_unified_kernel<KIND, false, false, OCC, 0, false, true, true>;
-    if (!ao) return count ? dev::render_unified_kernel<KIND, false, true, OCC> : dev::render_unified_kernel<KIND, false, false, OCC>;
-    return count ? dev::render_unified_kernel<KIND, true, true, OCC> : dev::render_unified_kernel<KIND, true, false, OCC>;
 }
 
-// simple::kernel / multi_hit / whitted epilogues: triangles, step loop
-template <int OCC>
-static kernel_fn pick_shade(bool count, int epi)
+template <size_t... I>
+static kernel_fn find_instance(size_t i, std::index_sequence<I...>)
 {
-    if (epi == 3)
-        return count ? dev::render_unified_kernel<dev::KIND_TRI, false, true, OCC, 3>
-                     : dev::render_unified_kernel<dev::KIND_TRI, false, false, OCC, 3>;
-    if (epi == 2)
-        return count ? dev::render_unified_kernel<dev::KIND_TRI, false, true, OCC, 2>
-                     : dev::render_unified_kernel<dev::KIND_TRI, false, false, OCC, 2>;
-    return count ? dev::render_unified_kernel<dev::KIND_TRI, false, true, OCC, 1>
-                 : dev::render_unified_kernel<dev::KIND_TRI, false, false, OCC, 1>;
+    static const kernel_fn table[NUM_KEYS + 1] = { instance_at<I>()..., nullptr };
+    return table[i];
 }
 
-// pathtracing::kernel (EPI 4, triangles): one frame, frames in flight (BATCH) and a pixel-sampler pass
-// (SAMPLED), at the default register budget and uncapped (occ 1); test counting on one-frame launches
-// EPI 5: the same set for a generic shading (tagged material records)
-template <int OCC, int EPI = 4>
-static kernel_fn pick_path(bool count, int sched)
+static kernel_fn select_variant(const instance_key& k)
 {
-    if (sched == 6) return dev::render_unified_kernel<dev::KIND_TRI, false, false, OCC, EPI, false, false, false, true>;
-    if (sched == 3) return dev::render_unified_kernel<dev::KIND_TRI, false, false, OCC, EPI, false, true>;
-    if (count) return OCC == 1 ? dev::render_unified_kernel<dev::KIND_TRI, false, true, 1, EPI> : nullptr;
-    return dev::render_unified_kernel<dev::KIND_TRI, false, false, OCC, EPI>;
-}
-
-template <int KIND>
-static kernel_fn pick(bool ao, bool count, int occ, int sched)
-{
-    if (occ == 8) return pick_occ<KIND, 8>(ao, count, sched);
-    if (occ == 6) return pick_occ<KIND, 6>(ao, count, sched);
-    if (occ == 5) return pick_occ<KIND, 5>(ao, count, sched);
-    return pick_occ<KIND, 1>(ao, count, sched);
-}
-
-// the overflow-stack instances exist at the register budgets the defaults choose from: AO 5 or 6
-// waves / SIMD (triangles), primary visibility 6 or 8
-template <int KIND>
-static kernel_fn pick_spill(bool ao, int occ, int sched)
-{
-    const int s = sched == 3 ? 5 : 4;
-    if (ao && KIND == dev::KIND_TRI && occ == 5) return pick_occ<KIND, 5>(true, false, s);
-    if (ao && KIND == dev::KIND_TRI && occ == 6) return pick_occ<KIND, 6>(true, false, s);
-    if (!ao && occ == 6) return pick_occ<KIND, 6>(false, false, s);
-    if (!ao && occ == 8) return pick_occ<KIND, 8>(false, false, s);
-    return nullptr;
-}
-
-// AO tail sharing instances: one-frame AO launches (sched 0) at the default 5 waves / SIMD, with and
-// without the stack overflow block
-template <int KIND>
-static kernel_fn pick_share(const launch_config& c)
-{
-    if (!c.ao || c.count || c.epi || c.occ != 5 || c.sched != 0) return nullptr;
-    return c.spill ? dev::render_unified_kernel<KIND, true, false, 5, 0, false, false, true, false, true>
-                   : dev::render_unified_kernel<KIND, true, false, 5, 0, false, false, false, false, true>;
-}
-
-static kernel_fn select_variant(const launch_config& c)
-{
-    if (c.share)
-        if (kernel_fn f = c.kind == dev::KIND_TRI ? pick_share<dev::KIND_TRI>(c) : pick_share<dev::KIND_SPHERE>(c)) return f;
-    if (c.epi == 4) return c.occ == 1 ? pick_path<1>(c.count, c.sched) : pick_path<PATH_OCC>(c.count, c.sched);
-    if (c.epi == 5) return c.occ == 1 ? pick_path<1, 5>(c.count, c.sched) : pick_path<PATH_OCC, 5>(c.count, c.sched);
-    if (c.epi) return c.occ == 8 ? pick_shade<8>(c.count, c.epi) : c.occ == 6 ? pick_shade<6>(c.count, c.epi)
-                    : c.occ == 5 ? pick_shade<5>(c.count, c.epi) : pick_shade<1>(c.count, c.epi);
-    if (c.spill)
-        return c.kind == dev::KIND_TRI ? pick_spill<dev::KIND_TRI>(c.ao, c.occ, c.sched)
-                                       : pick_spill<dev::KIND_SPHERE>(c.ao, c.occ, c.sched);
-    return c.kind == dev::KIND_TRI ? pick<dev::KIND_TRI>(c.ao, c.count, c.occ, c.sched)
-                                   : pick<dev::KIND_SPHERE>(c.ao, c.count, c.occ, c.sched);
-}
-
-bool render_spill_available(const launch_config& c)
-{
-    if (c.epi || c.count || (c.sched != 0 && c.sched != 3)) return false;
-    launch_config s = c;
-    s.spill = true;
-    return select_variant(s) != nullptr;
-}
-
-bool render_share_available(const launch_config& c)
-{
-    return c.kind == dev::KIND_TRI ? pick_share<dev::KIND_TRI>(c) != nullptr : pick_share<dev::KIND_SPHERE>(c) != nullptr;
+    return find_instance(key_index(k), std::make_index_sequence<NUM_KEYS>{});
 }
 
 size_t render_lds_bytes(const launch_config& c)
 {
-    size_t words = size_t(c.stack_cap) * c.block + (c.ao ? size_t(c.block / 64) * dev::AO_WAVE_WORDS : 0)
-                 + (c.epi == 2 ? size_t(5) * c.max_hits * c.block : 0)
-                 + (c.epi == 3 ? size_t(dev::WL_WORDS) * c.block : 0);
-    return words * 4;
+    return launch_lds_bytes(c, dev::AO_WAVE_WORDS, dev::WL_WORDS);
 }
 
 hipError_t launch_render(const render_params& p, const launch_config& c, int grid, hipStream_t s)
 {
-    hipLaunchKernelGGL(select_variant(c), dim3(grid), dim3(c.block), render_lds_bytes(c), s, p);
+    const kernel_fn f = select_variant(c);
+    if (!f) return hipErrorInvalidDeviceFunction;      // no such instance (plan_launch produces none)
+    hipLaunchKernelGGL(f, dim3(grid), dim3(c.block), render_lds_bytes(c), s, p);
     return hipGetLastError();
 }
 

@@ -15,6 +15,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 #include <string>
 #include <vector>
@@ -203,36 +204,36 @@ VRH_API int vrh_ctx_set_option(vrh_ctx* ctx, uint32_t option, int64_t value)
         // the traversal kernels are compiled for at most 256 threads per block (__launch_bounds__(256, ...)):
         // a larger block would break the register allocation's assumptions (a launch failure)
         VRH_CHECK(v % 64 == 0, std::string("vrh_ctx_set_option: ") + range->what);
-        ctx->opt_block = v; break;
-    case VRH_OPT_STACK_CAP: ctx->opt_stack = v; break;
+        ctx->opt.block = v; break;
+    case VRH_OPT_STACK_CAP: ctx->opt.stack = v; break;
     case VRH_OPT_AO_SCHEDULE:
         // the item loop (4) was removed in round 2: the step loop measured faster for every kernel
         if (v == 4) { set_error("vrh_ctx_set_option: the item-loop schedule was removed (the step loop is faster, profiles/r02_ab/ab18_sphere_schedule.log)"); return VRH_ERR_UNSUPPORTED; }
-        VRH_CHECK(v == 0 || v == 3, std::string("vrh_ctx_set_option: ") + range->what); ctx->opt_sched = v; break;
-    case VRH_OPT_WIDE_ANYHIT: ctx->opt_wide = v; break;
-    case VRH_OPT_DESCENT_CAP: ctx->opt_dcap = v; break;
+        VRH_CHECK(v == 0 || v == 3, std::string("vrh_ctx_set_option: ") + range->what); break;     // accepted; every kernel runs the step loop
+    case VRH_OPT_WIDE_ANYHIT: ctx->opt.wide = v; break;
+    case VRH_OPT_DESCENT_CAP: ctx->opt.dcap = v; break;
     case VRH_OPT_COOP_FETCH:
         // the cooperative quad fetch was removed in round 2 (measured slower, profiles/r01/ab_nocoop.log)
         if (v == 1) { set_error("vrh_ctx_set_option: the cooperative fetch was removed (it measured slower)"); return VRH_ERR_UNSUPPORTED; }
         break;
     case VRH_OPT_WAVE_TIMES: ctx->opt_wave_times = v; break;
-    case VRH_OPT_AO_CUT: ctx->opt_cut = v; break;
+    case VRH_OPT_AO_CUT: ctx->opt.cut = v; break;
     case VRH_OPT_AO_STEAL:
         // the AO tail stash was removed in round 3 (measured slower)
         if (v == 1) { set_error("vrh_ctx_set_option: the AO tail stash was removed (it measured slower)"); return VRH_ERR_UNSUPPORTED; }
         break;
-    case VRH_OPT_AO_SHARE: ctx->opt_share = v; break;
-    case VRH_OPT_AO_GATE: ctx->opt_gate = v; break;
-    case VRH_OPT_POP_ON_MISS: ctx->opt_pop = v; break;
-    case VRH_OPT_PAIR_LAYOUT: ctx->opt_layout = v; break;
-    case VRH_OPT_SCALAR_FETCH: ctx->opt_scalar = v; break;
-    case VRH_OPT_REFILL_MIN: ctx->opt_refill = v; break;
-    case VRH_OPT_BLOCKS_PER_CU: ctx->opt_bpc = v; break;
+    case VRH_OPT_AO_SHARE: ctx->opt.share = v; break;
+    case VRH_OPT_AO_GATE: ctx->opt.gate = v; break;
+    case VRH_OPT_POP_ON_MISS: ctx->opt.pop = v; break;
+    case VRH_OPT_PAIR_LAYOUT: ctx->opt.layout = v; break;
+    case VRH_OPT_SCALAR_FETCH: ctx->opt.scalar = v; break;
+    case VRH_OPT_REFILL_MIN: ctx->opt.refill = v; break;
+    case VRH_OPT_BLOCKS_PER_CU: ctx->opt.bpc = v; break;
     case VRH_OPT_WAVES_PER_SIMD:
         VRH_CHECK(v == 0 || v == 1 || v == 5 || v == 6 || v == 8, std::string("vrh_ctx_set_option: ") + range->what);
-        ctx->opt_occ = v; break;
-    case VRH_OPT_EXACT_MINMAX: ctx->opt_exact_minmax = v; break;
-    case VRH_OPT_XCD_QUEUES: ctx->opt_xcd_queues = v; break;
+        ctx->opt.occ = v; break;
+    case VRH_OPT_EXACT_MINMAX: ctx->opt.exact_minmax = v; break;
+    case VRH_OPT_XCD_QUEUES: ctx->opt.xcd_queues = v; break;
     case VRH_OPT_GROUP_UNITS:
     case VRH_OPT_QUAD_REFILL:
         // measured in round 4 and removed (slower: profiles/r04/ab/lane_layout/); 0 is accepted
@@ -252,7 +253,7 @@ VRH_API int vrh_ctx_set_option(vrh_ctx* ctx, uint32_t option, int64_t value)
         ctx->opt_async = v ? 1 : 0;
         break;
     }
-    case VRH_OPT_CLUSTER_TILES: ctx->opt_cluster = v; break;
+    case VRH_OPT_CLUSTER_TILES: ctx->opt.cluster = v; break;
     default: set_error("vrh_ctx_set_option: unknown option"); return VRH_ERR_INVALID;
     }
     return VRH_OK;
@@ -334,7 +335,7 @@ VRH_API int vrh_scene_upload(vrh_ctx* ctx, const void* nodes_v, uint32_t num_nod
     // preorder that puts each pair's child-0 pair right after it, so a parent and a child share a
     // 128-B line on half of the descent steps (31 % in the builder's order).  Links are renumbered;
     // the tree, the traversal order and every result are unchanged.
-    if (ctx->opt_layout == 1 && npairs > 1 && !(root & 0x80000000u))
+    if (ctx->opt.layout == 1 && npairs > 1 && !(root & 0x80000000u))
     {
         std::vector<uint32_t> perm(npairs, 0xFFFFFFFFu);
         uint32_t next = 0;
@@ -1135,9 +1136,20 @@ VRH_API int vrh_render_view(vrh_ctx* ctx, const vrh_scene* sc, vrh_rt* rt, const
     return render_sampled_impl(ctx, sc, rt, &cam, k, ps, frame_num, inv);
 }
 
+// ---- vrh_render: validate, plan (vrh_launch.h), fill render_params, choose where the launch runs,
+// diagnostics buffers, launch.  Every step takes what it reads as arguments.
 namespace {
-int render_batch_impl(vrh_ctx* ctx, const vrh_scene* sc, vrh_rt* rt, const vrh_camera* cams, uint32_t num_frames,
-                      const vrh_kernel_desc* k, const vrh_shard* shard, uint32_t frame_num, const sampler_pass* sp)
+
+// which rows of the target the launch writes
+struct frame_rows_t
+{
+    vrh_shard sh;
+    uint32_t local_bands;     // 8-row bands of one frame this shard renders
+    uint32_t frame_rows;      // frame f of the batch owns rows [f * frame_rows, (f + 1) * frame_rows) of the target
+};
+
+int validate_render(vrh_ctx* ctx, const vrh_scene* sc, vrh_rt* rt, const vrh_camera* cams, uint32_t num_frames,
+                    const vrh_kernel_desc* k, const vrh_shard* shard, frame_rows_t& rows)
 {
     VRH_CHECK(ctx && sc && rt && cams && k, "vrh_render: null argument");
     VRH_CHECK(rt->ctx == ctx && sc->ctx == ctx, "vrh_render: scene / render target of another context");
@@ -1189,173 +1201,62 @@ int render_batch_impl(vrh_ctx* ctx, const vrh_scene* sc, vrh_rt* rt, const vrh_c
         VRH_CHECK(sc->info.prim_kind != VRH_PRIM_TRI64 || uint64_t(hmask->num_tc) >= 3ull * (uint64_t(sc->info.max_prim_id) + 1),
                   "vrh_render: hit mask has fewer than 3 tex coords per prim_id");
     }
-    vrh_shard whole{ 0, 1, 0, 0 };
-    const vrh_shard& sh = shard ? *shard : whole;
-    VRH_CHECK(sh.count >= 1 && sh.index < sh.count, "vrh_render: bad shard");
-    const uint32_t local_bands = vrh_shard_bands(cam->height, sh.index, sh.count);
+    rows.sh = shard ? *shard : vrh_shard{ 0, 1, 0, 0 };
+    VRH_CHECK(rows.sh.count >= 1 && rows.sh.index < rows.sh.count, "vrh_render: bad shard");
+    rows.local_bands = vrh_shard_bands(cam->height, rows.sh.index, rows.sh.count);
     VRH_CHECK(rt->width == cam->width, "vrh_render: render target width != camera width");
-    // frame f of the batch owns rows [f * frame_rows, (f + 1) * frame_rows) of the target
-    uint32_t frame_rows = cam->height;
-    if (sh.packed)
+    rows.frame_rows = cam->height;
+    if (rows.sh.packed)
     {
-        frame_rows = rt->height / num_frames;
-        VRH_CHECK(frame_rows >= local_bands * VRH_BAND_ROWS || local_bands == 0, "vrh_render: packed target too small");
+        rows.frame_rows = rt->height / num_frames;
+        VRH_CHECK(rows.frame_rows >= rows.local_bands * VRH_BAND_ROWS || rows.local_bands == 0, "vrh_render: packed target too small");
     }
     else VRH_CHECK(rt->height == cam->height * num_frames, "vrh_render: render target height != camera height x frames");
     VRH_CHECK(uint64_t(rt->height) * rt->width < (1ull << 32), "vrh_render: render target too large");
+    return VRH_OK;
+}
 
-    // a depth-first traversal holds at most `max_depth` stack entries (>= 1 for the root push):
-    // `total` per lane, of which `cap` in LDS (the rest in a global overflow block, chosen below)
-    const uint32_t need = std::max<uint32_t>(sc->info.max_depth, 1u);
-    const uint32_t total = std::max((need + 3u) & ~3u, uint32_t(ctx->opt_stack));
-    uint32_t cap = ctx->opt_stack ? uint32_t(ctx->opt_stack) : total;
-    VRH_CHECK(cap >= 1u, "vrh_render: stack capacity option must be >= 1");
-    launch_config lc{};
-    lc.kind = sc->info.prim_kind == VRH_PRIM_TRI64 ? 0 : 1;
-    lc.ao = ao;
-    lc.count = (k->flags & VRH_KERNEL_COUNT_TESTS) != 0;
-    // AO tail sharing needs several waves per block (they share LDS): 4 unless the block is set
-    const bool ao_share = ctx->opt_share == 1 && ao && !list;
-    lc.block = ctx->opt_block ? ctx->opt_block : ao_share ? 256 : 64;
-    lc.share = ao_share;
-    lc.stack_cap = int(cap);
-    lc.epi = path ? (k->shading->gmaterials ? 5 : 4) : whitted ? 3 : multi ? 2 : shade ? 1 : 0;
-    lc.max_hits = multi ? int(k->max_hits) : 0;
-    // every kernel runs the step loop (the round-1 item loop for sphere primary visibility measured
-    // 6-9 % slower than the step loop with its round-2 defaults, profiles/r02_ab/ab18_sphere_schedule.log,
-    // and was removed)
-    lc.sched = 0;
-    if (list) lc.sched = 2;    // BVH lists: the step loop with the list merge
-    if (sp)
-    {
-        // a pixel-sampler pass runs its own instance (the plain ones keep their code and registers)
-        if (list || lc.count) { set_error("vrh_render_sampled: pixel samplers take a single BVH and no test counting"); return VRH_ERR_UNSUPPORTED; }
-        lc.sched = 6;
-    }
-    // frames in flight on the step loop (primary / AO, uncounted): the BATCH instantiation
-    if (lc.sched == 0 && num_frames > 1 && !lc.count && lc.epi == 0 && !hmask) lc.sched = 3;
-    if (lc.sched == 0 && num_frames > 1 && !lc.count && path) lc.sched = 3;
-    // shading epilogues: no VGPR cap (their lane state spills at 6 waves/SIMD; measured faster at 4,
-    // profiles/r01/shade/shade_bench.jsonl), except whitted, whose bounce surface lives in LDS (vrh_shade.h):
-    // 96 VGPRs without spills, 5 waves/SIMD, +0.7-2.1 % over 4 (profiles/r03_ab/whitted/).
-    // pathtracing::kernel (its lane state is registers only: throughput, sampler word, bounce): uncapped
-    // the instances take 99-100 VGPRs (4 waves/SIMD); capped at 5 waves/SIMD (PATH_OCC, vrh_kernels.h) they
-    // fit 94 (one frame, frames in flight) / 96 (sampler pass) VGPRs with no VGPR spill and no scratch
-    // (-Rpass-analysis=kernel-resource-usage), so 5 is the default -- not compared on the GPU against 4;
-    // waves_per_simd 1 and the counting variant (163 VGPRs) run uncapped.
-    // The instances over tagged materials (EPI 5, a generic shading): 96 / 96 / 96 VGPRs capped at PATH_OCC, no
-    // VGPR spill and no scratch either; uncapped 110 (4 waves/SIMD), the counting variant 165.
-    // AO on the step loop (round 5, the lean lane state: no VGPR spill or scratch at 80 VGPRs, also in
-    // the overflow-stack instances): 6 waves/SIMD, the LDS stack shrunk (below) to 16 entries so that 24
-    // waves fit a CU, the rest in the overflow block -- hf1M +4.8 %, hf10M +8.7 % over 5 waves
-    // (profiles/r05/occupancy/s6_*); AO tail sharing (opt-in) has 5-wave instances only.  Primary
-    // visibility: 8 waves/SIMD (64 VGPRs, no spill: hf1M +6.7-11 %, hf10M +3-9 %); spheres with frames in
-    // flight too, with the LDS stack shrunk to 20 entries so that 32 waves fit a CU (sph1M +4.8 % over 7
-    // waves, profiles/r05/sweepS/ -- at the whole 28-entry stack in LDS only 22 fit, -1 to -4 %,
-    // profiles/r05/occupancy/), but one frame per launch at 7 (the occupancy-6 instance: 8 waves with the
-    // overflow stack measured -8 %, profiles/r05/s26/); the counting variants keep 5 / 6 (at 8 they
-    // spill hundreds of VGPRs).  BVH lists run at 5 / 6
-    const int occ_ao = (ctx->opt_share == 1 || lc.count) ? 5 : 6;
-    const int occ_primary = (!lc.count && (lc.kind == 0 || num_frames > 1)) ? 8 : 6;
-    lc.occ = ctx->opt_occ ? ctx->opt_occ : whitted ? 5 : lc.epi ? 1 : lc.ao ? occ_ao : occ_primary;
-    if (sp) lc.occ = lc.ao ? 5 : 6;                    // the sampler instances exist at the defaults
-    if (path) lc.occ = (ctx->opt_occ == 1 || lc.count) ? 1 : PATH_OCC;
-    if (list) lc.occ = ao ? 5 : 6;
-    // tail sharing has instances for uncounted one-frame AO launches at 5 waves / SIMD only: where
-    // the kernel selection (vrh_kernels.hip pick_share, asked through render_share_available) has no
-    // SHARE instance the option changes nothing, not even the block size
-    if (lc.share && !render_share_available(lc))
-    {
-        lc.share = false;
-        if (!ctx->opt_block) lc.block = 64;
-    }
-    // auto: the LDS part of the stack shrinks (in steps of 4 entries) while LDS, not registers,
-    // limits the waves per CU -- a deep BVH (hf10M: depth 26) then keeps the register-bound
-    // occupancy and its few deepest entries go to the overflow block
-    // (the primary / AO step loops at their default register budgets have overflow-stack instances;
-    // every other kernel keeps its whole stack in LDS, as does an explicit VRH_OPT_STACK_CAP >= depth)
-    if (render_spill_available(lc) && (!ctx->opt_stack || cap < total))
-    {
-        lc.spill = true;
-        if (!ctx->opt_stack)
-        {
-            launch_config lo = lc;
-            lo.stack_cap = 4;
-            const int reg_bound = render_blocks_per_cu(lo);
-            while (lc.stack_cap > 4 && render_blocks_per_cu(lc) < reg_bound) lc.stack_cap -= 4;
-            // measured: hf10M AO 20 LDS entries +7 % over 24 at the same 20 waves / CU
-            // (profiles/r02_ab/ab6_stack.log); no BVH of depth <= 20 spills
-            if (total > 20u) lc.stack_cap = std::min(lc.stack_cap, 20);
-            cap = uint32_t(lc.stack_cap);
-        }
-        if (cap >= total) lc.spill = false;     // nothing overflows: the plain instance
-    }
-    else if (cap < total)
-        lc.stack_cap = int(cap = total);         // no overflow instance: the whole stack in LDS
-    if (render_lds_bytes(lc) > 160u * 1024u)
-    {
-        set_error("vrh_render: BVH depth " + std::to_string(sc->info.max_depth) + " needs more LDS stack than a CU has");
-        return VRH_ERR_UNSUPPORTED;
-    }
+// the device side of the plan: the kernels' LDS formula and the (cached) occupancy query
+struct render_device final : launch_device
+{
+    size_t lds_bytes(const launch_config& c) const override { return render_lds_bytes(c); }
+    int blocks_per_cu(const launch_config& c) const override { return render_blocks_per_cu(c); }
+};
 
-    int rc = select_device(ctx);
-    if (rc) return rc;
-    // asynchronous frames (VRH_OPT_ASYNC_FRAMES): whole-image frames go to a frame lane (below);
-    // shard renders (render groups record events on the context stream after their renders) and the
-    // timeline diagnostics stay on the context stream
-    const bool async = ctx->opt_async && !shard && !ctx->opt_wave_times;
-    if (!async)
-    {
-        rc = rt_wait(ctx, rt);
-        if (rc) return rc;
-    }
+int plan_render(const vrh_ctx* ctx, const vrh_scene* sc, uint32_t num_frames, const vrh_kernel_desc* k, bool sampler_pass,
+                launch_plan& plan)
+{
+    launch_inputs in;
+    in.kernel = k->kind; in.count_tests = (k->flags & VRH_KERNEL_COUNT_TESTS) != 0; in.max_hits = k->max_hits;
+    in.generic_shading = k->shading && k->shading->gmaterials;
+    in.sampler_pass = sampler_pass; in.hit_mask = k->hit_mask != nullptr; in.num_frames = num_frames;
+    in.prim_kind = sc->info.prim_kind; in.max_depth = sc->info.max_depth; in.num_roots = sc->num_roots;
+    in.device_bytes = sc->info.device_bytes;
+    in.finite_bounds = sc->finite_bounds; in.has_quads = sc->quads != nullptr; in.root_is_pair0 = sc->roots[0] == 0u;
+    in.opt = ctx->opt;
+    std::string err;
+    const int rc = plan_launch(in, render_device{}, plan, err);
+    if (rc) set_error(err);
+    return rc;
+}
 
-    render_params p{};
+int fill_params(render_params& p, const launch_plan& plan, const vrh_ctx* ctx, const vrh_scene* sc, const vrh_rt* rt,
+                const vrh_camera* cams, uint32_t num_frames, const vrh_kernel_desc* k, const frame_rows_t& rows,
+                uint32_t frame_num, const sampler_pass* sp)
+{
+    const vrh_camera* cam = cams;
+    const bool ao = k->kind == VRH_KERNEL_AO;
+    const bool multi = k->kind == VRH_KERNEL_MULTI_HIT;
     p.pairs = sc->pairs; p.prims = sc->prims; p.normals = sc->normals; p.root = sc->roots[0];
     p.num_roots = sc->num_roots;
     for (uint32_t i = 0; i < sc->num_roots; ++i) p.roots[i] = sc->roots[i];
     p.step_limit = sc->info.num_nodes + sc->info.num_indices + 16u;
-    // measured: profiles/r01/ab (AO: refill at 32 free lanes), profiles/r01/ab_primary (primary
-    // visibility: pop on a miss and a cap of 8 visits per descent step, +6 % on hf1M and +36 % on
-    // hf10M; both hurt AO)
-    const bool primary_step = !lc.ao && lc.epi == 0;
-    // AO step loop: refill once 24 lanes are free for scenes the 256 MB Infinity Cache holds, 28 above
-    // (profiles/r03_ab/refill/, 3 repetitions at 20 frames per launch: hf1M 24 vs 32 +0.6 %, hf10M
-    // 28 vs 32 +0.3 % and 24 -0.6 %)
-    p.refill_min = ctx->opt_refill ? uint32_t(ctx->opt_refill) : sc->info.device_bytes > (256ull << 20) ? 28u : 24u;
-    // primary visibility with frames in flight refills once 16 lanes are free: +3 % sph1M, +2 % hf1M,
-    // +1.8 % hf10M at 20 frames per launch (profiles/r02_ab/ab20_refill.log); simple::kernel and
-    // whitted once 8 are: +1-2.5 % / +1 % (profiles/r02_ab/shade_refill.jsonl); one-frame primary
-    // launches and multi_hit keep 1
-    const uint32_t refill_shade = (lc.epi == 1 || lc.epi == 3 || lc.epi == 4 || lc.epi == 5) ? 8u : 1u;
-    p.refill_min_primary = ctx->opt_refill ? uint32_t(ctx->opt_refill)
-                         : (primary_step && num_frames > 1) ? 16u : lc.epi ? refill_shade : 1u;
-    // primary visibility caps a lane's descent at 8 inner visits per step; at 8 waves / SIMD (round 5,
-    // profiles/r05/sweepP2/, 20 frames per launch, min over rounds) triangle scenes the Infinity Cache
-    // holds run best at 10 (hf1M +3 %; hf10M, above 256 MB, best at 8: 10 is -3 %), spheres at 6
-    // (sph1M +1.5 %)
-    const uint32_t dcap_primary = sc->info.prim_kind == VRH_PRIM_SPHERE48 ? 6u : sc->info.device_bytes > (256ull << 20) ? 8u : 10u;
-    p.descent_cap = ctx->opt_dcap ? uint32_t(ctx->opt_dcap) : primary_step ? dcap_primary : 0xFFFFFFFFu;
-    // shading epilogues (simple / multi_hit / whitted) pop on a miss too: +4-7 % (profiles/r01/shade/)
-    // AO (step loop): the tile's AO rays wait for its primaries (ao_gate), any-hit rays descend the
-    // 4-wide records and primaries pop on a miss -- together +6 % on hf1M and +10 % on hf10M
-    // (profiles/r02_ab/ab4_c4opts.log); each alone is within +-2 %
-    const bool ao_step = lc.ao;
-    p.ao_gate = (ctx->opt_gate == 1 || (ctx->opt_gate == 0 && ao_step)) ? 1u : 0u;
-    const bool pop = ctx->opt_pop == 1 || (ctx->opt_pop == 0 && (primary_step || lc.epi != 0 || ao_step));
-    p.step_flags = (pop ? 1u : 0u) | (ctx->opt_scalar == 2 ? 0u : 2u);
-    p.stack_cap = cap;
-    p.stack_total = lc.spill ? total : cap;
-    p.fast_ok = (sc->finite_bounds && !ctx->opt_exact_minmax) ? 1u : 0u;
-    p.quads = sc->quads;
-    // 4-wide any-hit records: auto on for the AO step loop (with ao_gate), off elsewhere
-    const bool wide = ctx->opt_wide == 1 || (ctx->opt_wide == 0 && ao_step);
-    // (the AO kernel restarts a 4-wide descent that would overflow its stack at pair 0: the root)
-    p.quad_ok = (sc->quads && p.fast_ok && wide && sc->roots[0] == 0u) ? 1u : 0u;
-    // per-tile entry cut of the 4-wide tree for AO rays (needs the gate: the tile's hits are known)
-    // entries nearest-first (+3.5 % over the cut order, profiles/r02_ab/ab33_ao_cut_order*.log)
-    p.ao_cut = (p.quad_ok && p.ao_gate && ctx->opt_cut != 2) ? (ctx->opt_cut == 3 ? 1u : 2u) : 0u;
-    p.ao_share = (lc.share && lc.block > 64) ? 1u : 0u;
+    p.refill_min = plan.refill_min; p.refill_min_primary = plan.refill_min_primary; p.descent_cap = plan.descent_cap;
+    p.ao_gate = plan.ao_gate; p.step_flags = plan.step_flags;
+    p.stack_cap = uint32_t(plan.cfg.stack_cap); p.stack_total = plan.stack_total;
+    p.fast_ok = plan.fast_ok;
+    p.quads = sc->quads; p.quad_ok = plan.quad_ok;
+    p.ao_cut = plan.ao_cut; p.ao_share = plan.ao_share;
     for (uint32_t f = 0; f < num_frames; ++f)
     {
         std::memcpy(p.cam[f].eye, cams[f].eye, 12); std::memcpy(p.cam[f].cam_u, cams[f].cam_u, 12);
@@ -1371,7 +1272,7 @@ int render_batch_impl(vrh_ctx* ctx, const vrh_scene* sc, vrh_rt* rt, const vrh_c
     }
     p.num_frames = num_frames;
     p.frame_num = frame_num;
-    p.frame_rows = frame_rows;
+    p.frame_rows = rows.frame_rows;
     p.width = cam->width; p.height = cam->height;
     p.width_f = float(cam->width); p.height_f = float(cam->height);
     p.samples = ao ? k->samples : 0; p.radius = k->radius; p.eps = k->eps;
@@ -1388,29 +1289,15 @@ int render_batch_impl(vrh_ctx* ctx, const vrh_scene* sc, vrh_rt* rt, const vrh_c
             std::memcpy(p.inv_proj, sp->inv_mats + 16, sizeof(p.inv_proj));
         }
     }
-    p.shard_index = sh.index; p.shard_count = sh.count; p.packed = sh.packed ? 1u : 0u;
+    p.shard_index = rows.sh.index; p.shard_count = rows.sh.count; p.packed = rows.sh.packed ? 1u : 0u;
     p.tiles_x = (cam->width + 7u) / 8u;
-    p.num_tiles = local_bands * p.tiles_x;        // a band is one row of 8x8 tiles
+    p.num_tiles = rows.local_bands * p.tiles_x;        // a band is one row of 8x8 tiles
     VRH_CHECK(uint64_t(p.num_tiles) * 64u * num_frames < (1ull << 32) && p.num_tiles < (1u << 26), "vrh_render: image too large");
     p.color = rt->color; p.prim_id = rt->prim_id; p.t = rt->t;
     p.occ = (k->flags & VRH_KERNEL_NO_OCC) ? nullptr : rt->occ;
     p.counters = ctx->counters;
-    // tile queues: per-XCD strips; with frames in flight the band-interleaved order (auto) for AO
-    // and for scenes larger than the 256 MB Infinity Cache.  Measured with a camera orbiting 0.5 deg
-    // per frame (profiles/r02_ab/ab31_tile_order_orbit_*.log): band order hf10M AO +3.5 %, hf10M
-    // primary +10 %, hf1M AO +0.3 %, but hf1M primary -2.8 % (its scene fits the MALL, and a
-    // strip's primaries then keep their XCD's L2); one-frame launches keep strips (ab30)
-    // AO with frames in flight: cluster order (every XCD on its own strip, the F frames of a cluster of
-    // 8 tiles handed out back to back): against the band order, round 4, same box, 20 frames per
-    // launch (profiles/r04/ab/cluster_hf{1M,10M}_{static,orbit}.log): hf10M +3.3 % (static camera) / +0.3 % (orbiting 0.5 deg per
-    // frame), hf1M +0.9 % / +2.3 %; clusters of 4-16 tiles alike, 240 (a whole band) no gain
-    const bool band_auto = num_frames > 1 && (lc.ao || sc->info.device_bytes > (256ull << 20));
-    const bool cluster_auto = num_frames > 1 && lc.ao;
-    p.xcd_queues = ctx->opt_xcd_queues == 2 ? 0u : ctx->opt_xcd_queues == 1 ? 1u
-                 : ctx->opt_xcd_queues == 3 ? 2u : ctx->opt_xcd_queues == 4 ? 3u
-                 : cluster_auto ? 3u : (band_auto ? 2u : 1u);
-    p.cluster = ctx->opt_cluster ? uint32_t(ctx->opt_cluster) : 8u;
-    if (shade)
+    p.xcd_queues = plan.xcd_queues; p.cluster = plan.cluster;
+    if (plan.cfg.epi != EPI_PLAIN)
     {
         if (k->shading->gmaterials) p.shade.gmaterials = k->shading->gmaterials;
         else p.shade.materials = k->shading->materials;
@@ -1421,156 +1308,149 @@ int render_batch_impl(vrh_ctx* ctx, const vrh_scene* sc, vrh_rt* rt, const vrh_c
         std::memcpy(p.shade.ambient, k->ambient, 16);
         for (int i = 0; i < 3; ++i) p.shade.amb[i] = p.shade.ambient[i] * p.shade.ambient[3];   // plastic.inl:13-16
     }
-    p.num_bounces = (whitted || path) ? k->num_bounces : 0u;
-    if (hmask && sc->info.prim_kind == VRH_PRIM_TRI64)
-        p.hmask = dev::hit_mask_params{ hmask->tc, hmask->mask, hmask->w, hmask->h };
+    p.num_bounces = (k->kind == VRH_KERNEL_WHITTED || k->kind == VRH_KERNEL_PATHTRACING) ? k->num_bounces : 0u;
+    if (k->hit_mask && sc->info.prim_kind == VRH_PRIM_TRI64)
+        p.hmask = dev::hit_mask_params{ k->hit_mask->tc, k->hit_mask->mask, k->hit_mask->w, k->hit_mask->h };
     if (multi)
     {
         p.max_hits = k->max_hits;
         p.mh_prim_id = rt->mh_prim_id;
         p.mh_t = rt->mh_t;
     }
+    return VRH_OK;
+}
 
-    int per_cu = render_blocks_per_cu(lc);
-    if (ctx->opt_bpc) per_cu = std::min(per_cu, ctx->opt_bpc);
-    const int waves_per_block = lc.block / 64;
-    const uint64_t units = uint64_t(num_frames) * p.num_tiles;
-    int grid = std::max(1, int(std::min<uint64_t>(uint64_t(ctx->num_cus) * per_cu, (units + waves_per_block - 1) / waves_per_block)));
+// device blocks grown on demand: `stream` is drained first (no launch still uses the old blocks), the
+// old blocks are freed and the new ones allocated; `have` is 0 while there are none
+struct grown_block { void** ptr; size_t bytes; };
+int grow_blocks(hipStream_t stream, size_t& have, size_t want, std::initializer_list<grown_block> blocks)
+{
+    if (want <= have) return VRH_OK;
+    VRH_HIP(hipStreamSynchronize(stream));
+    for (const grown_block& b : blocks)
+        if (*b.ptr) { (void)hipFree(*b.ptr); *b.ptr = nullptr; }
+    have = 0;
+    for (const grown_block& b : blocks) VRH_HIP(hipMalloc(b.ptr, b.bytes));
+    have = want;
+    return VRH_OK;
+}
 
-    // where the launch runs: the context stream with its counter / overflow blocks, or a frame lane
-    hipStream_t S = ctx->stream;
-    unsigned long long* ctr = ctx->counters;
-    void** spill = &ctx->spill;
-    size_t* spill_bytes = &ctx->spill_bytes;
-    vrh_ctx::lane_t* L = nullptr;
-    bool via_scratch = false;
-    float4* dst_color = p.color; uint32_t* dst_pid = p.prim_id; float* dst_t = p.t; uint8_t* dst_occ = p.occ;
-    if (async)
+// where the launch runs: the context stream with its counter / overflow blocks, or a frame lane
+struct launch_site
+{
+    hipStream_t stream;
+    unsigned long long* counters;
+    void** spill; size_t* spill_bytes;   // the overflow block of that stream
+    vrh_ctx::lane_t* lane;        // null: the context stream
+    bool via_scratch;             // the frame renders into the lane's scratch target
+    bool fields[4];               // the target's colour, prim id, t, occlusion are written
+};
+
+// (an asynchronous frame redirects p's output pointers to the lane's scratch target where it must)
+int choose_site(vrh_ctx* ctx, vrh_rt* rt, const vrh_kernel_desc* k, uint32_t num_frames, const sampler_pass* sp, bool async,
+                render_params& p, launch_site& site)
+{
+    site = launch_site{ ctx->stream, ctx->counters, &ctx->spill, &ctx->spill_bytes, nullptr, false,
+                        { p.color != nullptr, p.prim_id != nullptr, p.t != nullptr, p.occ != nullptr } };
+    if (!async) return VRH_OK;
+    // cuda_sched issues a frame and returns (cuda_sched.inl:306-320): frames go round robin over the
+    // frame lanes, so this frame's waves fill the CUs the earlier frames' launch tails leave idle
+    const uint32_t li = ctx->next_lane;
+    vrh_ctx::lane_t* L = &ctx->lane[li];
+    if (!L->stream)
     {
-        // cuda_sched issues a frame and returns (cuda_sched.inl:306-320): frames go round robin over the
-        // frame lanes, so this frame's waves fill the CUs the earlier frames' launch tails leave idle
-        const uint32_t li = ctx->next_lane;
-        L = &ctx->lane[li];
-        if (!L->stream)
-        {
-            VRH_HIP(hipStreamCreateWithFlags(&L->stream, hipStreamDefault));    // blocking: see vrh_ctx_create
-            VRH_HIP(hipEventCreateWithFlags(&L->done, hipEventDisableTiming));
-        }
-        if (!ctx->main_mark) VRH_HIP(hipEventCreateWithFlags(&ctx->main_mark, hipEventDisableTiming));
-        if (!rt->lane_written) VRH_HIP(hipEventCreateWithFlags(&rt->lane_written, hipEventDisableTiming));
-        ctx->next_lane = (ctx->next_lane + 1u) % ctx->num_lanes;
-        S = L->stream;
-        ctr = L->counters;
-        spill = &L->spill;
-        spill_bytes = &L->spill_bytes;
-        // after everything issued on the context stream before this call (clears, uploads, frames there)
-        VRH_HIP(hipEventRecord(ctx->main_mark, ctx->stream));
-        VRH_HIP(hipStreamWaitEvent(S, ctx->main_mark, 0));
-        if (rt->written_pending) VRH_HIP(hipStreamWaitEvent(S, rt->written, 0));
-        // a primary / AO frame of one image through a sampler that does not read the target writes every
-        // field of the target at every pixel of its scissor box: it may go through the scratch target,
-        // and it supersedes a pending scratch copy into this target of no larger box (that frame's pixels
-        // would never be seen: they are dropped, not copied).  Any other pending copy into this target,
-        // and one still in this lane's scratch target, is issued first.
-        const bool scratch_ok = num_frames == 1 && (k->kind == VRH_KERNEL_PRIMARY || ao) && (!sp || sp->blend == 0);
-        const uint32_t* cl = p.cam[0].clip;
-        const bool fields[4] = { dst_color != nullptr, dst_pid != nullptr, dst_t != nullptr, dst_occ != nullptr };
-        for (uint32_t l = 0; l < uint32_t(VRH_MAX_FRAME_LANES); ++l)
-        {
-            vrh_ctx::lane_t& Q = ctx->lane[l];
-            if (!Q.pending_rt) continue;
-            const uint32_t* qc = Q.pending_clip;
-            const bool covers = Q.pending_rt == rt && scratch_ok && cl[0] <= qc[0] && cl[1] <= qc[1] && cl[2] >= qc[2]
-                                && cl[3] >= qc[3] && fields[0] == Q.pending_fields[0] && fields[1] == Q.pending_fields[1]
-                                && fields[2] == Q.pending_fields[2] && fields[3] == Q.pending_fields[3];
-            if (covers) Q.pending_rt = nullptr;
-            else if (Q.pending_rt == rt || l == li) VRH_HIP(ctx_flush_pending(ctx, int(l)));
-        }
-        // the target's last writer is the other lane, not yet joined: write order must hold.  A frame that
-        // may go through the scratch target renders there now, and its copy becomes the lane's pending
-        // copy (issued when something else needs the target, dropped when a later frame supersedes it);
-        // anything else waits for that writer
-        const bool other_writer = rt->lane >= 0 && rt->lane != int(li) && rt->lane_epoch == ctx->join_epoch;
-        if (other_writer)
-        {
-            if (scratch_ok)
-            {
-                const size_t n = size_t(rt->width) * rt->height;
-                if (n > L->pixels)
-                {
-                    VRH_HIP(hipStreamSynchronize(S));
-                    for (void** q : { (void**)&L->color, (void**)&L->prim_id, (void**)&L->t, (void**)&L->occ })
-                        if (*q) { (void)hipFree(*q); *q = nullptr; }
-                    L->pixels = 0;
-                    VRH_HIP(hipMalloc(&L->color, n * sizeof(float4)));
-                    VRH_HIP(hipMalloc(&L->prim_id, n * sizeof(uint32_t)));
-                    VRH_HIP(hipMalloc(&L->t, n * sizeof(float)));
-                    VRH_HIP(hipMalloc(&L->occ, n));
-                    L->pixels = n;
-                }
-                p.color = dst_color ? L->color : nullptr;
-                p.prim_id = dst_pid ? L->prim_id : nullptr;
-                p.t = dst_t ? L->t : nullptr;
-                p.occ = dst_occ ? L->occ : nullptr;
-                via_scratch = true;
-            }
-            else
-                VRH_HIP(hipStreamWaitEvent(S, rt->lane_written, 0));
-        }
+        VRH_HIP(hipStreamCreateWithFlags(&L->stream, hipStreamDefault));    // blocking: see vrh_ctx_create
+        VRH_HIP(hipEventCreateWithFlags(&L->done, hipEventDisableTiming));
     }
-    p.counters = ctr;
+    if (!ctx->main_mark) VRH_HIP(hipEventCreateWithFlags(&ctx->main_mark, hipEventDisableTiming));
+    if (!rt->lane_written) VRH_HIP(hipEventCreateWithFlags(&rt->lane_written, hipEventDisableTiming));
+    ctx->next_lane = (ctx->next_lane + 1u) % ctx->num_lanes;
+    const hipStream_t S = L->stream;
+    site.lane = L; site.stream = S; site.counters = L->counters;
+    site.spill = &L->spill; site.spill_bytes = &L->spill_bytes;
+    // after everything issued on the context stream before this call (clears, uploads, frames there)
+    VRH_HIP(hipEventRecord(ctx->main_mark, ctx->stream));
+    VRH_HIP(hipStreamWaitEvent(S, ctx->main_mark, 0));
+    if (rt->written_pending) VRH_HIP(hipStreamWaitEvent(S, rt->written, 0));
+    // a primary / AO frame of one image through a sampler that does not read the target writes every
+    // field of the target at every pixel of its scissor box: it may go through the scratch target,
+    // and it supersedes a pending scratch copy into this target of no larger box (that frame's pixels
+    // would never be seen: they are dropped, not copied).  Any other pending copy into this target,
+    // and one still in this lane's scratch target, is issued first.
+    const bool scratch_ok = num_frames == 1 && (k->kind == VRH_KERNEL_PRIMARY || k->kind == VRH_KERNEL_AO) && (!sp || sp->blend == 0);
+    const uint32_t* cl = p.cam[0].clip;
+    const bool* fields = site.fields;
+    for (uint32_t l = 0; l < uint32_t(VRH_MAX_FRAME_LANES); ++l)
+    {
+        vrh_ctx::lane_t& Q = ctx->lane[l];
+        if (!Q.pending_rt) continue;
+        const uint32_t* qc = Q.pending_clip;
+        const bool covers = Q.pending_rt == rt && scratch_ok && cl[0] <= qc[0] && cl[1] <= qc[1] && cl[2] >= qc[2]
+                            && cl[3] >= qc[3] && fields[0] == Q.pending_fields[0] && fields[1] == Q.pending_fields[1]
+                            && fields[2] == Q.pending_fields[2] && fields[3] == Q.pending_fields[3];
+        if (covers) Q.pending_rt = nullptr;
+        else if (Q.pending_rt == rt || l == li) VRH_HIP(ctx_flush_pending(ctx, int(l)));
+    }
+    // the target's last writer is the other lane, not yet joined: write order must hold.  A frame that
+    // may go through the scratch target renders there now, and its copy becomes the lane's pending
+    // copy (issued when something else needs the target, dropped when a later frame supersedes it);
+    // anything else waits for that writer
+    const bool other_writer = rt->lane >= 0 && rt->lane != int(li) && rt->lane_epoch == ctx->join_epoch;
+    if (other_writer && scratch_ok)
+    {
+        const size_t n = size_t(rt->width) * rt->height;
+        const int rc = grow_blocks(S, L->pixels, n, { { (void**)&L->color, n * sizeof(float4) }, { (void**)&L->prim_id, n * sizeof(uint32_t) },
+                                                      { (void**)&L->t, n * sizeof(float) }, { (void**)&L->occ, n } });
+        if (rc) return rc;
+        p.color = fields[0] ? L->color : nullptr;
+        p.prim_id = fields[1] ? L->prim_id : nullptr;
+        p.t = fields[2] ? L->t : nullptr;
+        p.occ = fields[3] ? L->occ : nullptr;
+        site.via_scratch = true;
+    }
+    else if (other_writer)
+        VRH_HIP(hipStreamWaitEvent(S, rt->lane_written, 0));
+    return VRH_OK;
+}
 
-    // the stack overflow blocks of the persistent grid (grown on demand; the stream is drained
-    // first, so no launch still uses the old block)
+// the stack overflow blocks of the persistent grid and the diagnostics buffers of this launch
+int launch_buffers(vrh_ctx* ctx, const launch_config& lc, uint32_t num_frames, int grid, const launch_site& site, render_params& p)
+{
+    p.counters = site.counters;
     if (lc.spill)
     {
         const size_t bytes = size_t(grid) * (p.stack_total - p.stack_cap) * size_t(lc.block) * sizeof(uint32_t);
-        if (bytes > *spill_bytes)
-        {
-            VRH_HIP(hipStreamSynchronize(S));
-            if (*spill) (void)hipFree(*spill);
-            *spill = nullptr;
-            *spill_bytes = 0;
-            VRH_HIP(hipMalloc(spill, bytes));
-            *spill_bytes = bytes;
-        }
-        p.stack_spill = static_cast<uint32_t*>(*spill);
+        const int rc = grow_blocks(site.stream, *site.spill_bytes, bytes, { { site.spill, bytes } });
+        if (rc) return rc;
+        p.stack_spill = static_cast<uint32_t*>(*site.spill);
     }
 
     // per-wave timeline of this launch (diagnostic, VRH_OPT_WAVE_TIMES)
     ctx->wave_times_used = 0;
-    if (ctx->opt_wave_times && (lc.sched == 0 || lc.sched == 3))
+    if (ctx->opt_wave_times && !lc.list && !lc.sampled)
     {
-        const size_t n = size_t(grid) * waves_per_block;
-        if (n > ctx->wave_times_n)
-        {
-            VRH_HIP(hipStreamSynchronize(ctx->stream));
-            if (ctx->wave_times) (void)hipFree(ctx->wave_times);
-            ctx->wave_times = nullptr;
-            ctx->wave_times_n = 0;
-            VRH_HIP(hipMalloc(&ctx->wave_times, n * 2 * sizeof(unsigned long long)));
-            ctx->wave_times_n = n;
-        }
+        const size_t n = size_t(grid) * (lc.block / 64);
+        const int rc = grow_blocks(ctx->stream, ctx->wave_times_n, n, { { (void**)&ctx->wave_times, n * 2 * sizeof(unsigned long long) } });
+        if (rc) return rc;
         p.wave_times = ctx->wave_times;
         ctx->wave_times_used = n;
     }
     ctx->tile_times_used = 0;
     if (ctx->opt_wave_times == 2 && lc.count && lc.ao && num_frames == 1 && p.num_tiles > 0)
     {
-        if (p.num_tiles > ctx->tile_times_n)
-        {
-            VRH_HIP(hipStreamSynchronize(ctx->stream));
-            if (ctx->tile_times) (void)hipFree(ctx->tile_times);
-            ctx->tile_times = nullptr;
-            ctx->tile_times_n = 0;
-            VRH_HIP(hipMalloc(&ctx->tile_times, size_t(p.num_tiles) * 3 * sizeof(unsigned long long)));
-            ctx->tile_times_n = p.num_tiles;
-        }
-        VRH_HIP(hipMemsetAsync(ctx->tile_times, 0, size_t(p.num_tiles) * 3 * sizeof(unsigned long long), ctx->stream));
+        const size_t bytes = size_t(p.num_tiles) * 3 * sizeof(unsigned long long);
+        const int rc = grow_blocks(ctx->stream, ctx->tile_times_n, p.num_tiles, { { (void**)&ctx->tile_times, bytes } });
+        if (rc) return rc;
+        VRH_HIP(hipMemsetAsync(ctx->tile_times, 0, bytes, ctx->stream));
         p.tile_times = ctx->tile_times;
         ctx->tile_times_used = p.num_tiles;
     }
+    return VRH_OK;
+}
 
+int launch_and_record(vrh_ctx* ctx, vrh_rt* rt, const render_params& p, const launch_config& lc, int grid, const launch_site& site)
+{
+    const hipStream_t S = site.stream;
     const uint32_t slot = ctx->frames % VRH_MAX_TIMED_FRAMES;
     while (ctx->ev_start.size() <= slot)
     {
@@ -1580,14 +1460,14 @@ int render_batch_impl(vrh_ctx* ctx, const vrh_scene* sc, vrh_rt* rt, const vrh_c
         ctx->ev_start.push_back(a);
         ctx->ev_stop.push_back(b);
     }
-    VRH_HIP(hipMemsetAsync(ctr, 0, COUNTERS_FRAME * sizeof(unsigned long long), S));
+    VRH_HIP(hipMemsetAsync(site.counters, 0, COUNTERS_FRAME * sizeof(unsigned long long), S));
     VRH_HIP(hipEventRecord(ctx->ev_start[slot], S));
     if (p.num_tiles > 0) VRH_HIP(launch_render(p, lc, grid, S));
     VRH_HIP(hipEventRecord(ctx->ev_stop[slot], S));
-    if (async)
+    if (vrh_ctx::lane_t* L = site.lane)
     {
         const uint32_t* cl = p.cam[0].clip;
-        if (via_scratch)
+        if (site.via_scratch)
         {
             // the scissor box of the scratch target -- every pixel a primary / AO frame writes -- is this
             // lane's pending copy into the target (ctx_flush_pending: after the target's previous writer)
@@ -1595,10 +1475,7 @@ int render_batch_impl(vrh_ctx* ctx, const vrh_scene* sc, vrh_rt* rt, const vrh_c
             {
                 L->pending_rt = rt;
                 for (int i = 0; i < 4; ++i) L->pending_clip[i] = cl[i];
-                L->pending_fields[0] = dst_color != nullptr;
-                L->pending_fields[1] = dst_pid != nullptr;
-                L->pending_fields[2] = dst_t != nullptr;
-                L->pending_fields[3] = dst_occ != nullptr;
+                for (int i = 0; i < 4; ++i) L->pending_fields[i] = site.fields[i];
             }
         }
         else
@@ -1612,7 +1489,7 @@ int render_batch_impl(vrh_ctx* ctx, const vrh_scene* sc, vrh_rt* rt, const vrh_c
     }
     else
         rt->lane = -1;
-    ctx->last_counters = ctr;
+    ctx->last_counters = site.counters;
     ctx->last_slot = slot;
     ctx->frames++;
 
@@ -1621,9 +1498,45 @@ int render_batch_impl(vrh_ctx* ctx, const vrh_scene* sc, vrh_rt* rt, const vrh_c
     ctx->last.grid_blocks = uint32_t(grid);
     ctx->last.block_threads = uint32_t(lc.block);
     ctx->last.stack_depth = p.stack_total;
-    ctx->last.frames = num_frames;
+    ctx->last.frames = p.num_frames;
     ctx->have_frame = true;
     return VRH_OK;
+}
+
+int render_batch_impl(vrh_ctx* ctx, const vrh_scene* sc, vrh_rt* rt, const vrh_camera* cams, uint32_t num_frames,
+                      const vrh_kernel_desc* k, const vrh_shard* shard, uint32_t frame_num, const sampler_pass* sp)
+{
+    frame_rows_t rows;
+    int rc = validate_render(ctx, sc, rt, cams, num_frames, k, shard, rows);
+    if (rc) return rc;
+    rc = select_device(ctx);        // the plan's occupancy queries ask the context's device
+    if (rc) return rc;
+    launch_plan plan;
+    rc = plan_render(ctx, sc, num_frames, k, sp != nullptr, plan);
+    if (rc) return rc;
+    // asynchronous frames (VRH_OPT_ASYNC_FRAMES): whole-image frames go to a frame lane (choose_site);
+    // shard renders (render groups record events on the context stream after their renders) and the
+    // timeline diagnostics stay on the context stream
+    const bool async = ctx->opt_async && !shard && !ctx->opt_wave_times;
+    if (!async)
+    {
+        rc = rt_wait(ctx, rt);
+        if (rc) return rc;
+    }
+
+    render_params p{};
+    rc = fill_params(p, plan, ctx, sc, rt, cams, num_frames, k, rows, frame_num, sp);
+    if (rc) return rc;
+    const int waves_per_block = plan.cfg.block / 64;
+    const uint64_t units = uint64_t(num_frames) * p.num_tiles;
+    const int grid = std::max(1, int(std::min<uint64_t>(uint64_t(ctx->num_cus) * plan.per_cu, (units + waves_per_block - 1) / waves_per_block)));
+
+    launch_site site;
+    rc = choose_site(ctx, rt, k, num_frames, sp, async, p, site);
+    if (rc) return rc;
+    rc = launch_buffers(ctx, plan.cfg, num_frames, grid, site, p);
+    if (rc) return rc;
+    return launch_and_record(ctx, rt, p, plan.cfg, grid, site);
 }
 } // namespace
 
