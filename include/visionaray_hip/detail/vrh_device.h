@@ -27,6 +27,8 @@
 #include <cstdint>
 #include <type_traits>
 
+#include "vrh_sampler.h"
+
 #ifndef VRH_SCALAR_UNIFORM
 #define VRH_SCALAR_UNIFORM 1   // wave-uniform pair fetches through the scalar cache (ray_step)
 #endif
@@ -304,6 +306,14 @@ struct test_counts
     // summed over groups (the hardware's accesses); acc_ideal = per distinct piece ceil(lanes / 4)
     uint64_t acc4, acc_ideal;
     uint64_t acc_kind[5];     // acc4 by load kind (VMEM_*)
+    // where a wave's time goes (counting variant of the AO step loop; wave-uniform values, ticks of
+    // wall_clock64()): handing out AO rays (the cut build and rays claimed from a sibling included),
+    // handing out primaries, the traversal step, and the whole loop (the rest is tile bookkeeping,
+    // occlusion bits and pixel writes)
+    uint64_t t_ao, t_primary, t_step, t_loop;
+    // AO hand-outs: events (a wave starting AO rays in its idle lanes), rays started, and runs of
+    // started rays that share a hit slot (a run's lanes need the same normal and basis)
+    uint32_t ho_events, ho_rays, ho_runs;
 };
 // kinds of the counted vector-memory instructions
 constexpr uint32_t VMEM_PRIM = 0, VMEM_QUAD = 1, VMEM_PAIR = 2, VMEM_NORMAL = 3, VMEM_STORE = 4;
@@ -662,33 +672,17 @@ __device__ __forceinline__ ray_t make_ray(f3 ori, f3 dir)
     return r;
 }
 
-// SURVEY.md Appendix A counter hash
-__device__ __forceinline__ uint32_t wang(uint32_t a)
-{
-    a = (a ^ 61u) ^ (a >> 16);
-    a = a + (a << 3);
-    a = a ^ (a >> 4);
-    a = a * 0x27d4eb2du;
-    return a ^ (a >> 15);
-}
-__device__ __forceinline__ float uniform01(uint32_t k) { return (float)(wang(k) >> 8) * (1.0f / 16777216.0f); }
+// SURVEY.md Appendix A counter hash (wang, uniform01) and the AO disk sample: vrh_sampler.h
 
 // per-frame sampler offset: the reference seeds its sampler anew every frame (cuda_sched.inl:38-45,
 // 79; ao/main.cpp passes ++frame_num, :245).  The Appendix-A counter of frame n is shifted by
 // n * 0x9E3779B1 (u32 wrap); frame 0 keeps the Appendix-A counter exactly (the parity fixtures).
 __host__ __device__ __forceinline__ uint32_t frame_salt(uint32_t frame_num) { return frame_num * 0x9E3779B1u; }
 
-// Appendix A Malley sample s of pixel p -> direction in the (u, v, n) basis (ao/main.cpp:218-226)
-__device__ __forceinline__ f3 ao_direction(uint32_t p, uint32_t s, f3 bu, f3 bv, f3 n, uint32_t salt)
+// Appendix A Malley sample (sx, sy) (vrh_sampler.h ao_disk_sample) -> direction in the (u, v, n)
+// basis (ao/main.cpp:223-226)
+__device__ __forceinline__ f3 ao_direction(float sx, float sy, f3 bu, f3 bv, f3 n)
 {
-    float sx = 0.0f, sy = 0.0f;
-    for (uint32_t k = 0; k < 16; ++k)
-    {
-        uint32_t ctr = ((p * 8u + s) * 16u + k) * 2u + salt;
-        float xa = 2.0f * uniform01(ctr) - 1.0f;
-        float ya = 2.0f * uniform01(ctr + 1u) - 1.0f;
-        if (xa * xa + ya * ya < 1.0f) { sx = xa; sy = ya; break; }
-    }
     float sz = __builtin_sqrtf(tmax(0.0f, 1.0f - sx * sx - sy * sy));
     return normalize((sx * bu + sy * bv) + sz * n);
 }

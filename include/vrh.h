@@ -225,7 +225,21 @@ typedef struct {
     /* l1_group_accesses by kind: primitives, 4-wide records, binary pair records, AO normals,
      * output stores */
     uint64_t l1_group_by_kind[5];
-} vrh_frame_stats;
+} vrh_frame_stats;   /* the caller allocates it: its size is part of the ABI and stays */
+
+/* VRH_KERNEL_COUNT_TESTS of the AO kernel (vrh_last_handout_stats; zeros for other frames) */
+typedef struct {
+    /* where the waves' time goes, in ticks of the device's constant clock summed over the waves --
+     * handing out AO rays to idle lanes (the tile's cut build included), handing out primaries, the
+     * traversal step, and the whole refilling loop (the rest: tile bookkeeping, occlusion bits, pixel
+     * writes).  The clock reads perturb the kernel: shares, not times. */
+    uint64_t ao_handout_ticks, primary_handout_ticks, step_ticks, loop_ticks;
+    /* AO hand-outs: events (one wave starting AO rays in its idle lanes), rays started, and runs of
+     * consecutive started rays that share a hit slot (rays / runs = lanes that need the same normal
+     * and basis) */
+    uint64_t ao_handout_events, ao_handout_rays, ao_handout_slot_runs;
+    uint64_t reserved[9];
+} vrh_handout_stats;
 
 typedef struct {
     uint32_t num_nodes, num_prims, num_indices, prim_kind;
@@ -451,6 +465,7 @@ VRH_API int vrh_render_batch(vrh_ctx* ctx, const vrh_scene* scene, vrh_rt* rt, c
                              uint32_t frame_num);
 VRH_API int vrh_sync(vrh_ctx* ctx);
 VRH_API int vrh_last_frame_stats(vrh_ctx* ctx, vrh_frame_stats* stats);   /* syncs */
+VRH_API int vrh_last_handout_stats(vrh_ctx* ctx, vrh_handout_stats* stats);   /* of the same frame; syncs */
 /* VRH_OPT_WAVE_TIMES: (start, end) clock ticks of every wave of the last launch, 2 * count values
  * into out (capacity values at most); ticks_per_ms = the constant wall clock's rate; syncs */
 VRH_API int vrh_get_wave_times(vrh_ctx* ctx, uint64_t* out, uint64_t capacity, uint64_t* count, double* ticks_per_ms);

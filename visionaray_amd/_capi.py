@@ -108,6 +108,12 @@ class vrh_frame_stats(C.Structure):
                 ("l1_group_by_kind", C.c_uint64 * 5)]
 
 
+class vrh_handout_stats(C.Structure):
+    _fields_ = [("ao_handout_ticks", C.c_uint64), ("primary_handout_ticks", C.c_uint64), ("step_ticks", C.c_uint64),
+                ("loop_ticks", C.c_uint64), ("ao_handout_events", C.c_uint64), ("ao_handout_rays", C.c_uint64),
+                ("ao_handout_slot_runs", C.c_uint64), ("reserved", C.c_uint64 * 9)]
+
+
 class vrh_scene_view(C.Structure):
     _fields_ = [("pairs", C.c_void_p), ("prims", C.c_void_p), ("normals", C.c_void_p), ("root", C.c_uint32),
                 ("max_depth", C.c_uint32), ("prim_kind", C.c_uint32), ("finite_bounds", C.c_uint32),
@@ -199,6 +205,7 @@ SIGNATURES = {
     "vrh_matrix_inverse": (None, [_vp, _vp]),
     "vrh_sync": (C.c_int, [_vp]),
     "vrh_last_frame_stats": (C.c_int, [_vp, C.POINTER(vrh_frame_stats)]),
+    "vrh_last_handout_stats": (C.c_int, [_vp, C.POINTER(vrh_handout_stats)]),
     "vrh_stats_reset": (C.c_int, [_vp]),
     "vrh_get_accum_stats": (C.c_int, [_vp, C.POINTER(vrh_accum_stats)]),
     "vrh_rt_download": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),

@@ -178,6 +178,12 @@ class Context:
         capi.check("vrh_last_frame_stats", self.handle, C.byref(s))
         return {k: (list(getattr(s, k)) if isinstance(getattr(s, k), C.Array) else getattr(s, k)) for k, _ in s._fields_}
 
+    def last_handout_stats(self):
+        """vrh_last_handout_stats: the AO counting kernel's time spans and hand-out counts of the last frame."""
+        s = capi.vrh_handout_stats()
+        capi.check("vrh_last_handout_stats", self.handle, C.byref(s))
+        return {k: getattr(s, k) for k, _ in s._fields_ if k != "reserved"}
+
     def wave_times(self):
         """(start, end) of every wave of the last launch in ms from the launch's first start, or
         None (VRH_OPT_WAVE_TIMES off).  Diagnostic of the launch's ramp-up and tail."""

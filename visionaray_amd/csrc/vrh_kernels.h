@@ -104,6 +104,9 @@ struct render_params
 constexpr int COUNTERS_FRAME = 208;     // u64 words reset before every frame
 constexpr int COUNTERS_LINES = 80;      // [80] L1 128-B lines, [81] wave-level vector-memory instructions, [82] 16-B requests,
                                         // [83] 4-lane-group accesses, [84] ideal-grouping accesses (counting variant)
+constexpr int COUNTERS_HANDOUT = 96;    // [96..99] wave time (wall_clock64 ticks summed over waves): AO hand-out, primary hand-out,
+                                        // traversal step, whole loop; [100..102] AO hand-out events, rays, slot runs (counting
+                                        // variant of the AO step loop, test_counts::t_* / ho_*)
 constexpr int COUNTERS_TOTAL = 208;     // u64 words [208], [209]: totals
 constexpr int COUNTERS_WORDS = 256;
 constexpr int VRH_MAX_FRAME_LANES = 4;  // asynchronous frames: frame lanes of a context, at most

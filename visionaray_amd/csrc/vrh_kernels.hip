@@ -110,7 +110,8 @@ __device__ __forceinline__ bool tile_pixel(const render_params& P, uint32_t unit
 }
 
 // per-wave totals (rays, hits, test counts): one atomic set per wave, at the end of the kernel
-template <bool COUNT>
+// (AO: the AO step loop's time spans and hand-out counts as well)
+template <bool COUNT, bool AO>
 __device__ __forceinline__ void flush_totals(const render_params& P, uint32_t lane, uint64_t rays_total,
                                              uint64_t hits_total, const test_counts& cnt)
 {
@@ -152,6 +153,16 @@ __device__ __forceinline__ void flush_totals(const render_params& P, uint32_t la
             atomicAdd(P.counters + COUNTERS_LINES + 3, a4);
             atomicAdd(P.counters + COUNTERS_LINES + 4, ai);
             for (int k = 0; k < 5; ++k) atomicAdd(P.counters + COUNTERS_LINES + 5 + k, ak[k]);
+            if constexpr (AO)
+            {
+                atomicAdd(P.counters + COUNTERS_HANDOUT, (unsigned long long)cnt.t_ao);       // wave-uniform values
+                atomicAdd(P.counters + COUNTERS_HANDOUT + 1, (unsigned long long)cnt.t_primary);
+                atomicAdd(P.counters + COUNTERS_HANDOUT + 2, (unsigned long long)cnt.t_step);
+                atomicAdd(P.counters + COUNTERS_HANDOUT + 3, (unsigned long long)cnt.t_loop);
+                atomicAdd(P.counters + COUNTERS_HANDOUT + 4, (unsigned long long)cnt.ho_events);
+                atomicAdd(P.counters + COUNTERS_HANDOUT + 5, (unsigned long long)cnt.ho_rays);
+                atomicAdd(P.counters + COUNTERS_HANDOUT + 6, (unsigned long long)cnt.ho_runs);
+            }
         }
     }
 }
@@ -352,22 +363,58 @@ __device__ __forceinline__ uint32_t lane_rank(uint64_t mask)
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
 }
 
+// The AO hand-out path (start_ao: the idle lanes of a wave take new AO rays while the busy lanes'
+// rays stand still) is a latency chain; VRH_AO_HANDOUT's bits switch its shortenings for A/B builds
+// (every combination computes the same bits): 1 the disk sample is searched while
+// the hit record and the normal are in flight, 2 the search forms four candidates at a time
+// (vrh_sampler.h first_accepted_of16).  Reading the cut entries four at a time before testing them
+// measured slower and is not kept.
+// The tail-sharing and pixel-sampler instances keep the sequential path (HO = 0): at their register
+// budgets the shortened one cost a VGPR spill (sphere share instance) or scratch (sampler pass).
+#ifndef VRH_AO_HANDOUT
+#define VRH_AO_HANDOUT 3
+#endif
+constexpr uint32_t HO_REORDER = 1u, HO_SEARCH4 = 2u;
+
+template <uint32_t HO>
+__device__ __forceinline__ void handout_disk_sample(uint32_t p, uint32_t s, uint32_t salt, float& sx, float& sy)
+{
+    if (HO & HO_SEARCH4) { ao_disk_sample(p, s, salt, sx, sy); return; }
+    sx = 0.0f; sy = 0.0f;                                    // one candidate after the other
+    for (uint32_t k = 0; k < 16; ++k)
+    {
+        float xa, ya;
+        ao_disk_candidate(p, s, salt, k, xa, ya);
+        if (xa * xa + ya * ya < 1.0f) { sx = xa; sy = ya; break; }
+    }
+}
+
 // AO ray s of hit slot `slot` whose pixel has global index p in frame f of the launch
 // (ao/main.cpp:216-238 with the Appendix-A sampler, offset by the frame number)
-template <bool COUNT>
+template <bool COUNT, uint32_t HO>
 __device__ __forceinline__ ray_t ao_ray(const render_params& P, const float* recs, uint32_t slot, uint32_t s,
                                         uint32_t p, uint32_t f, test_counts& cnt)
 {
+    // the slot's record (one aligned 16-B LDS read) and the gather of its normal are issued first and
+    // land while the disk sample is searched; the basis is formed after the search (HO_REORDER)
+    static_assert(AO_REC_WORDS == 4 && AO_WAVE_WORDS % 4 == 0, "a hit record is one aligned 16-B read");
     const float* sr = recs + slot * AO_REC_WORDS;
-    f3 pos = mk3(sr[0], sr[1], sr[2]);
-    const float4* np = P.normals + __float_as_uint(sr[3]);
+    float4 rec;
+    if constexpr ((HO & HO_REORDER) != 0u) rec = *reinterpret_cast<const float4*>(sr);
+    else rec = make_float4(sr[0], sr[1], sr[2], sr[3]);
+    f3 pos = mk3(rec.x, rec.y, rec.z);
+    const float4* np = P.normals + __float_as_uint(rec.w);
     const float4 nn = *np;                                             // get_normal.h:26-37
     if (COUNT) count_vmem(cnt, np, 1u, VMEM_NORMAL);
+    const uint32_t salt = frame_salt(P.frame_num + f);
+    float sx = 0.0f, sy = 0.0f;
+    if (HO & HO_REORDER) handout_disk_sample<HO>(p, s, salt, sx, sy);
     f3 n = mk3(nn.x, nn.y, nn.z);
     // vector3.inl:357-367 make_orthonormal_basis(u, v, w = n)
     f3 bv = fabsf(n.x) > fabsf(n.y) ? normalize(mk3(-n.z, 0.0f, n.x)) : normalize(mk3(0.0f, n.z, -n.y));
     f3 bu = cross(bv, n);
-    f3 d = ao_direction(p, s, bu, bv, n, frame_salt(P.frame_num + f));
+    if (!(HO & HO_REORDER)) handout_disk_sample<HO>(p, s, salt, sx, sy);
+    f3 d = ao_direction(sx, sy, bu, bv, n);
     return make_ray(pos + d * P.eps, d);
 }
 
@@ -912,6 +959,7 @@ __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params 
         // own, which the 6-wave instances spilled
         // owner wave << 12 (the wave whose tile the ray belongs to: this one unless it helps a sibling)
         uint32_t tag = 0;
+        constexpr uint32_t HO = (SHARE || SAMPLED) ? 0u : uint32_t(VRH_AO_HANDOUT);   // hand-out path of this instance
         // AO ray `cand` (slot-major: slot cand / S, sample cand % S) of the tile `tile` whose hit records,
         // slot pixels and cut are recs_ / spx / cut_, cutn (this wave's, or a sibling's it helps)
         auto start_ao = [&](const float* recs_, const uint8_t* spx, const float* cut_, uint32_t cutn, uint32_t tile,
@@ -920,7 +968,7 @@ __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params 
             const uint32_t slot = (cand * P.samples_recip) >> 20, smp = cand - slot * S;
             uint32_t x, y, orow, fr;
             tile_pixel(P, tile, spx[par * 64u + slot], x, y, orow, fr);
-            r = ao_ray<COUNT>(P, recs_, slot, smp, y * P.width + x, fr, cnt);
+            r = ao_ray<COUNT, HO>(P, recs_, slot, smp, y * P.width + x, fr, cnt);
             best_t = FMAX; best_prim = 0; steps = 0; max_t = P.radius; any = true;
             bk = 0; res_t = FMAX; res_prim = 0;
             const bool fin = finite_ray(r);
@@ -951,8 +999,27 @@ __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params 
             tag = slot | (smp << 6) | (par << 11) | (SHARE ? owner << 12 : 0u) | (fin ? 0u : TAG_NONFINITE);
             rays_total += 1;
         };
+        // counting instance: where the wave's time goes (test_counts::t_*) and its AO hand-outs.  `go`:
+        // this lane starts AO ray cand of a hand-out whose first ray is `first`
+        uint64_t tk = 0;
+        auto span = [&](uint64_t& acc) {
+            if constexpr (COUNT) { const uint64_t now = wall_clock64(); acc += now - tk; tk = now; }
+        };
+        auto count_handout = [&](bool go, uint32_t cand, uint32_t first) {
+            if constexpr (COUNT)
+            {
+                const uint64_t started = __ballot(go);
+                const uint32_t slot = (cand * P.samples_recip) >> 20;
+                cnt.ho_events += started != 0ull ? 1u : 0u;
+                cnt.ho_rays += (uint32_t)__popcll(started);
+                cnt.ho_runs += (uint32_t)__popcll(__ballot(go && (cand == first || cand == slot * S)));
+            }
+        };
+        uint64_t t_rest = 0;
+        if constexpr (COUNT) { tk = wall_clock64(); cnt.t_loop = tk; }
         for (;;)
         {
+            span(t_rest);
             // 1. the draining tile is done when its last AO ray is: write its hit pixels
             if (tileD != NONE && (parD ? inflight1 : inflight0) == 0u && (!shD || lds_ld(&sh[SH_HELP]) == 0u))
             {
@@ -1034,12 +1101,14 @@ __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params 
                 }
                 const uint32_t cand = base + lane_rank(idle);
                 const uint32_t n = base < avail ? min(avail - base, want) : 0u;
+                count_handout(mode == IDLE && cand < avail, cand, base);
                 if (mode == IDLE && cand < avail)
                     start_ao(recs, slot_px, cut, cutN, tileC, parC, cand, wave);
                 issC = shC ? min(avail, base + want) : issC + n;
                 if (parC) inflight1 += n; else inflight0 += n;
                 idle = __ballot(mode == IDLE);
             }
+            span(cnt.t_ao);
             if (idle && tileC != NONE && handedC < 64u)
             {
                 const uint32_t k = handedC + lane_rank(idle);
@@ -1059,6 +1128,7 @@ __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params 
                 }
                 pendC += (uint32_t)__popcll(__ballot(started));
             }
+            span(cnt.t_primary);
             // 3b. nothing of its own left to hand out once the queues are dry: idle lanes claim AO
             //     rays of a sibling wave's published tile (their occlusion bits go to the sibling's
             //     masks, the sibling writes the pixels once its helpers' rays are done)
@@ -1090,6 +1160,7 @@ __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params 
                         if (lane == 0u && got < want) atomicSub(&so[SH_HELP], want - got);
                         if (got == 0u) continue;
                         const uint32_t rk = lane_rank(hidle);
+                        count_handout(mode == IDLE && rk < got, b + rk, b);
                         if (mode == IDLE && rk < got)
                             start_ao(reinterpret_cast<const float*>(ao_o), reinterpret_cast<const uint8_t*>(ao_o + AO_SLOT_PX),
                                      reinterpret_cast<const float*>(ao_o + AO_CUT), uu(lds_ld(&so[SH_CUTN])), t,
@@ -1098,6 +1169,7 @@ __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params 
                     }
                 }
             }
+            span(cnt.t_ao);
             const bool busy = mode != IDLE;
             if (__ballot(busy) == 0ull)
             {
@@ -1119,6 +1191,7 @@ __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params 
             }
             if constexpr (LIST)
                 if (busy && rc < 0) rc = list_next(P, any, bk, res_t, res_prim, best_t, best_prim, st, resume);
+            span(cnt.t_step);
             if (COUNT) count_wave(cnt, busy);
             // 5. finished AO rays: record occlusion, retire from their tile's in-flight count
             const bool ao_done = mode == AORAY && rc != 0;
@@ -1179,10 +1252,11 @@ __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params 
             }
             if (rc != 0) mode = IDLE;
         }
+        if constexpr (COUNT) cnt.t_loop = wall_clock64() - cnt.t_loop;
     }
 
     if (wt_slot && __lane_id() == 0u) wt_slot[1] = wall_clock64();
-    flush_totals<COUNT>(P, __lane_id(), rays_total, hits_total, cnt);
+    flush_totals<COUNT, AO>(P, __lane_id(), rays_total, hits_total, cnt);
 }
 
 // un-interleave gathered packed shards [count][rows_per_shard][W] into the full image (vrh_plan.h

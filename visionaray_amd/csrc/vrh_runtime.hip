@@ -1647,6 +1647,27 @@ VRH_API int vrh_last_frame_stats(vrh_ctx* ctx, vrh_frame_stats* stats)
     return VRH_OK;
 }
 
+VRH_API int vrh_last_handout_stats(vrh_ctx* ctx, vrh_handout_stats* stats)
+{
+    VRH_CHECK(ctx && stats, "vrh_last_handout_stats: null");
+    VRH_CHECK(ctx->have_frame, "vrh_last_handout_stats: no frame rendered yet");
+    int rc = select_device(ctx);
+    if (rc) return rc;
+    VRH_HIP(hipEventSynchronize(ctx->ev_stop[ctx->last_slot]));
+    unsigned long long c[7];
+    VRH_HIP(hipMemcpy(c, ctx->last_counters + COUNTERS_HANDOUT, sizeof(c), hipMemcpyDeviceToHost));
+    vrh_handout_stats s{};
+    s.ao_handout_ticks = c[0];
+    s.primary_handout_ticks = c[1];
+    s.step_ticks = c[2];
+    s.loop_ticks = c[3];
+    s.ao_handout_events = c[4];
+    s.ao_handout_rays = c[5];
+    s.ao_handout_slot_runs = c[6];
+    *stats = s;
+    return VRH_OK;
+}
+
 VRH_API int vrh_stats_reset(vrh_ctx* ctx)
 {
     VRH_CHECK(ctx, "vrh_stats_reset: null");
