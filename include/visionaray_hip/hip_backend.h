@@ -733,6 +733,11 @@ vrh_point_light to_point_light(L const& l)
     return r;
 }
 inline vrh_point_light to_point_light(vrh_point_light const& l) { return l; }
+// the reference's tex_filter_mode (Nearest 0, Linear 1; the spline filters have no counterpart) and
+// tex_address_mode (Wrap 0, Mirror 1, Clamp 2; Border has none): texture/forward.h:18-34.  A mode without
+// a counterpart is passed on as it is, and vrh_shading_set_textures refuses it.
+inline uint32_t to_tex_filter(int mode) { return uint32_t(mode); }
+inline uint32_t to_tex_address(int mode) { return uint32_t(mode); }
 
 inline uint32_t binding_of(normals_per_face_binding const&) { return VRH_NORMALS_PER_FACE; }
 inline uint32_t binding_of(normals_per_vertex_binding const&) { return VRH_NORMALS_PER_VERTEX; }
@@ -769,6 +774,36 @@ public:
                               "vrh_shading_create");
         }
         shading_.reset(s, [](vrh_shading* p) { vrh_shading_free(p); });
+    }
+
+    // The tex_coords / textures arguments of make_kernel_params(binding, prims, normals, tex_coords,
+    // materials, textures, lights, ...) (kernels.h:396-437).  tex_coords: 3 per prim_id (the model's
+    // tex_coords, any type with .x / .y); textures: one per material (indexed by geom_id), any range of
+    // objects with the interface of texture_ref<vector<4, unorm<8>>, 2>: width(), height(), data() (4 bytes
+    // per texel), get_filter_mode() (Nearest / Linear), get_address_mode() (indexable by axis: Wrap, Mirror,
+    // Clamp); width or height 0 is the dummy.  The texels are copied (vrh_shading_set_textures); an empty
+    // range detaches the textures.
+    template <typename TexCoords, typename Textures>
+    void set_textures(TexCoords const& tex_coords, Textures const& textures)
+    {
+        std::vector<float> tc;
+        for (auto const& c : tex_coords) { tc.push_back(c.x); tc.push_back(c.y); }
+        std::vector<vrh_texture_desc> descs;
+        for (auto const& t : textures)
+        {
+            vrh_texture_desc d{};
+            d.width = uint32_t(t.width());
+            d.height = uint32_t(t.height());
+            d.pixels = d.width && d.height ? static_cast<const void*>(t.data()) : nullptr;
+            d.format = VRH_TEX_RGBA8;
+            d.filter = hip_detail::to_tex_filter(int(t.get_filter_mode()));
+            auto const am = t.get_address_mode();
+            d.address[0] = hip_detail::to_tex_address(int(am[0]));
+            d.address[1] = hip_detail::to_tex_address(int(am[1]));
+            descs.push_back(d);
+        }
+        hip_detail::check(vrh_shading_set_textures(ctx_->get(), shading_.get(), tc.data(), uint32_t(tc.size() / 2), descs.data(),
+                                                   uint32_t(descs.size())), "vrh_shading_set_textures");
     }
 
     vrh_shading* handle() const { return shading_.get(); }

@@ -15,6 +15,7 @@
 
 #include "hip_backend.h"
 
+#include <array>
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
@@ -237,6 +238,42 @@ struct model
     std::vector<tex_coord_type> tex_coords;
     std::vector<material_type> materials;
     aabb bbox;
+};
+
+// The texture types hip_shading::set_textures reads, for programs without the reference's headers: the
+// enums of texture/forward.h:18-34 with the reference's values, 8-bit normalised texels, and the minimal
+// texture_ref<vector<4, unorm<8>>, 2> (texture/detail/texture_common.h:169-209, texture2d.h): a view of
+// width x height texels that somebody else owns.
+enum tex_address_mode { Wrap = 0, Mirror, Clamp, Border };
+enum tex_filter_mode { Nearest = 0, Linear, BSpline, BSplineInterpol, CardinalSpline };
+
+template <unsigned Bits> struct unorm;
+template <> struct unorm<8> { uint8_t value; };
+
+template <typename T, size_t Dim> class texture_ref;
+template <typename T>
+class texture_ref<T, 2>
+{
+public:
+    using value_type = T;
+    texture_ref() = default;
+    texture_ref(size_t w, size_t h) : width_(w), height_(h) {}
+    void reset(T const* data) { data_ = data; }
+    T const* data() const { return data_; }
+    size_t width() const { return width_; }
+    size_t height() const { return height_; }
+    void set_filter_mode(tex_filter_mode mode) { filter_mode_ = mode; }
+    tex_filter_mode get_filter_mode() const { return filter_mode_; }
+    void set_address_mode(size_t index, tex_address_mode mode) { address_mode_[index] = mode; }
+    void set_address_mode(tex_address_mode mode) { address_mode_[0] = address_mode_[1] = mode; }
+    std::array<tex_address_mode, 2> const& get_address_mode() const { return address_mode_; }
+    tex_address_mode get_address_mode(size_t index) const { return address_mode_[index]; }
+
+private:
+    T const* data_ = nullptr;
+    size_t width_ = 0, height_ = 0;
+    tex_filter_mode filter_mode_ = Nearest;
+    std::array<tex_address_mode, 2> address_mode_{ { Wrap, Wrap } };
 };
 
 namespace constants

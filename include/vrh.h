@@ -21,6 +21,9 @@
  *                                                                     kernels.h:357-389 (device copies of
  *                         the material / light arrays, as viewer.cpp:501-523 uploads them)
  *   vrh_shading_create_generic <- the same with generic_material<...> materials  generic_material.h
+ *   vrh_shading_set_textures <- the tex_coords / textures arguments of the textured make_kernel_params
+ *                                                                     kernels.h:396-437, get_surface.h:422-454
+ *   vrh_pnm_load       <- pnm_image::load (binary P5 / P6)           src/common/pnm_image.cpp
  *   VRH_KERNEL_SIMPLE  <- simple::kernel<Params>                     detail/simple.inl:19-83
  *   VRH_KERNEL_WHITTED <- whitted::kernel<Params>                    detail/whitted.inl:186-277
  *   VRH_KERNEL_PATHTRACING <- pathtracing::kernel<Params>            detail/pathtracing.inl:29-121
@@ -430,6 +433,63 @@ VRH_API int vrh_shading_create(vrh_ctx* ctx, const vrh_plastic* materials, uint3
 VRH_API int vrh_shading_create_generic(vrh_ctx* ctx, const vrh_material* materials, uint32_t num_materials,
                                        const vrh_point_light* lights, uint32_t num_lights, vrh_shading** out);
 VRH_API int vrh_shading_free(vrh_shading* shading);
+
+/* Diffuse maps <- the `tex_coords` and `textures` arguments of make_kernel_params(binding, prims, normals,
+ * tex_coords, materials, textures, lights, ...) (kernels.h:396-437).  get_surface samples
+ * textures[geom_id] at the hit (get_surface.h:422-454) with the coordinate
+ * lerp(tc[3 prim_id], tc[3 prim_id + 1], tc[3 prim_id + 2], u, v) (get_tex_coord.h:23-39, math.h:466-475);
+ * a texture of width or height 0 is the reference's dummy: tex_color 1.  The model's texture type is
+ * texture<vector<4, unorm<8>>, 2> (src/common/model.h:29), which the OBJ loader sets to Wrap / Linear
+ * (obj_loader.cpp:394-396).  tex2D for it (texture/detail/sampler2d.h:88-127, filter/nearest.h:51-73,
+ * filter/linear.h:72-118, filter/common.h:27-84) filters the texels as integers 0..255 in float, truncates
+ * the result to int and normalises it with unorm_to_float<8> (math/detail/unorm.inl:28-31); restated
+ * bit for bit in visionaray_hip/detail/vrh_texture.h, which also says how the reference's reads of texel N
+ * of an axis are reproduced without ever reading outside the array.
+ * tex_color enters plastic::shade's diffuse term only (plastic.inl:21-37, 180-183; the ambient term is
+ * untouched), plastic::sample and matte::sample as tex_color * sample_impl(...) (plastic.inl:62,
+ * matte.inl:64) and emissive as (tex_color * ce) * ls (emissive.inl:89); mirror does not read it.
+ * RGB8 and R8 pixels are expanded to RGBA8 on the host as swizzle.h:196-224 does for the loader's
+ * reset(..., PF_RGBA8, AlphaIsOne) calls: (r, g, b, 255) and (r, r, r, 255). */
+enum vrh_texture_format { VRH_TEX_RGBA8 = 0, VRH_TEX_RGB8 = 1, VRH_TEX_R8 = 2 };
+enum vrh_texture_filter { VRH_TEX_NEAREST = 0, VRH_TEX_LINEAR = 1 };
+enum vrh_texture_address { VRH_TEX_WRAP = 0, VRH_TEX_MIRROR = 1, VRH_TEX_CLAMP = 2 };
+#define VRH_TEX_MAX_DIM 32768u
+#define VRH_TEX_MAX_TEXELS (1u << 28)
+#define VRH_TEX_MAX_COORD 1048576.0f   /* 2^20 */
+typedef struct {
+    const void* pixels;       /* width x height texels of `format`, rows in order, no padding */
+    uint32_t width, height;   /* either 0: the dummy texture (pixels is not read)             */
+    uint32_t format;          /* vrh_texture_format                                           */
+    uint32_t filter;          /* vrh_texture_filter                                           */
+    uint32_t address[2];      /* vrh_texture_address of x and y                               */
+} vrh_texture_desc;
+/* Attaches texture coordinates (num_tex_coords float pairs, three per prim_id) and textures (indexed by
+ * geom_id: num_textures must equal the shading's material count) to a shading, plastic or generic; both
+ * are copied to the device, descriptors that share a pixel pointer, size and format are uploaded once.
+ * num_textures 0 detaches them: the shading renders as before.  Waits for the context's frames first.
+ * VRH_ERR_INVALID: an unknown enum value, a count mismatch, num_tex_coords not a multiple of 3, a
+ * dimension above VRH_TEX_MAX_DIM or width x height above VRH_TEX_MAX_TEXELS, a texture coordinate that is
+ * not finite or exceeds VRH_TEX_MAX_COORD in magnitude (interpolated coordinates stay within the vertices'
+ * range, so every float -> int conversion of the sampler is defined).
+ * At render time: a scene with a prim_id >= num_tex_coords / 3 -> VRH_ERR_INVALID; VRH_KERNEL_MULTI_HIT,
+ * a hit mask or VRH_KERNEL_COUNT_TESTS with a textured shading -> VRH_ERR_UNSUPPORTED. */
+VRH_API int vrh_shading_set_textures(vrh_ctx* ctx, vrh_shading* shading, const float* tex_coords,
+                                     uint32_t num_tex_coords, const vrh_texture_desc* textures, uint32_t num_textures);
+/* the host build of the shared sampler: rgba_out[4 i ..] = the RGBA8 sample tex2D(desc, coords[2 i ..])
+ * before its normalisation (255, 255, 255, 255 for the dummy); the checks of vrh_shading_set_textures */
+VRH_API int vrh_tex2d_host(const vrh_texture_desc* desc, const float* coords, uint32_t n, uint8_t* rgba_out);
+
+/* Binary PNM images <- pnm_image::load (src/common/pnm_image.cpp): P5 (one channel) and P6 (three) with
+ * 8-bit samples, comment lines in the header, rows in file order; a max value other than 255 is rescaled
+ * as pnm_image.cpp:88-97 does: uint8(v * ((1.0 / max) * 255)).  A missing, malformed or truncated file ->
+ * VRH_ERR_INVALID; every other format (plain PNM, 16-bit samples, any other image type) ->
+ * VRH_ERR_UNSUPPORTED. */
+typedef struct {
+    uint8_t* pixels;          /* width x height x channels, owned by the image: vrh_pnm_free    */
+    uint32_t width, height, channels, max_value;
+} vrh_pnm_image;
+VRH_API int vrh_pnm_load(const char* filename, vrh_pnm_image* out);
+VRH_API int vrh_pnm_free(vrh_pnm_image* image);
 
 /* render targets.  vrh_rt_alloc owns its buffers (flags = vrh_rt_flags); vrh_rt_wrap borrows
  * caller device pointers (any may be NULL), e.g. torch tensors used for the RCCL gather. */

@@ -11,20 +11,20 @@ from .api import (BVH_NODE_DTYPE, DEGREES_TO_RADIANS, GROUP_ID_BYTES, MATERIAL_D
                   MATERIAL_MIRROR, MATERIAL_PLASTIC, PLASTIC_DTYPE, POINT_LIGHT_DTYPE,
                   SPHERE_DTYPE, TRIANGLE_DTYPE, Context, ao_kernel, broadcast_scene, build_index_bvh, camera, closest_hit_kernel,
                   device_count, emissive, face_normals, generic_materials, generic_shading, hip_buffer_rt, hip_index_bvh, hip_sched,
-                  hit_mask, index_bvh, load_obj, make_sched_params, make_spheres, make_triangles, matrix_inverse, matte, mirror, model,
+                  hit_mask, index_bvh, load_obj, load_pnm, make_sched_params, make_spheres, make_triangles, matrix_inverse, matte, mirror, model,
                   multi_hit_kernel, normals_per_face_binding, normals_per_vertex_binding, pathtracing_kernel, pixel_sampler,
                   plastic,
                   point_light, render, render_batch, render_group, render_sampled, render_sharded, render_view, sah_cost, shading,
-                  shard_bands, simple_kernel, unshard, view_camera, whitted_kernel, with_hit_mask)
+                  shard_bands, simple_kernel, tex_address, tex_filter, texture, unshard, view_camera, whitted_kernel, with_hit_mask)
 
 __all__ = [
     "BVH_NODE_DTYPE", "DEGREES_TO_RADIANS", "GROUP_ID_BYTES", "MATERIAL_DTYPE", "MATERIAL_EMISSIVE", "MATERIAL_MATTE",
     "MATERIAL_MIRROR", "MATERIAL_PLASTIC", "PLASTIC_DTYPE", "POINT_LIGHT_DTYPE", "SPHERE_DTYPE",
     "TRIANGLE_DTYPE", "Context", "VrhError", "_capi", "ao_kernel", "broadcast_scene", "build_index_bvh", "camera", "closest_hit_kernel",
     "device_count", "emissive", "face_normals", "generic_materials", "generic_shading", "hip_buffer_rt", "hip_index_bvh", "hip_sched",
-    "hit_mask", "index_bvh", "load_obj", "make_sched_params", "make_spheres", "make_triangles", "matrix_inverse", "matte", "mirror", "model",
+    "hit_mask", "index_bvh", "load_obj", "load_pnm", "make_sched_params", "make_spheres", "make_triangles", "matrix_inverse", "matte", "mirror", "model",
     "multi_hit_kernel", "normals_per_face_binding", "normals_per_vertex_binding", "pathtracing_kernel", "pixel_sampler",
     "plastic",
     "point_light", "render", "render_batch", "render_group", "render_sampled", "render_sharded", "render_view", "sah_cost",
-    "shading", "shard_bands", "simple_kernel", "unshard", "view_camera", "whitted_kernel", "with_hit_mask",
+    "shading", "shard_bands", "simple_kernel", "tex_address", "tex_filter", "texture", "unshard", "view_camera", "whitted_kernel", "with_hit_mask",
 ]

@@ -150,6 +150,23 @@ class vrh_wire_layout(C.Structure):
 
 VRH_WIRE_ABSENT = (1 << 64) - 1
 
+VRH_TEX_RGBA8, VRH_TEX_RGB8, VRH_TEX_R8 = 0, 1, 2
+VRH_TEX_NEAREST, VRH_TEX_LINEAR = 0, 1
+VRH_TEX_WRAP, VRH_TEX_MIRROR, VRH_TEX_CLAMP = 0, 1, 2
+VRH_TEX_MAX_DIM = 32768
+VRH_TEX_MAX_TEXELS = 1 << 28
+VRH_TEX_MAX_COORD = float(1 << 20)
+
+
+class vrh_texture_desc(C.Structure):
+    _fields_ = [("pixels", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32), ("format", C.c_uint32),
+                ("filter", C.c_uint32), ("address", C.c_uint32 * 2)]
+
+
+class vrh_pnm_image(C.Structure):
+    _fields_ = [("pixels", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32), ("channels", C.c_uint32),
+                ("max_value", C.c_uint32)]
+
 
 class VrhError(RuntimeError):
     def __init__(self, fn, code, msg):
@@ -244,6 +261,10 @@ SIGNATURES = {
     "vrh_obj_material_name": (C.c_char_p, [_vp, _u32]),
     "vrh_obj_material_texture": (C.c_char_p, [_vp, _u32]),
     "vrh_obj_free": (C.c_int, [_vp]),
+    "vrh_shading_set_textures": (C.c_int, [_vp, _vp, _vp, _u32, _vp, _u32]),
+    "vrh_tex2d_host": (C.c_int, [_vp, _vp, _u32, _vp]),
+    "vrh_pnm_load": (C.c_int, [C.c_char_p, _vp]),
+    "vrh_pnm_free": (C.c_int, [_vp]),
 }
 
 _lib = None

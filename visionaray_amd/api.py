@@ -658,6 +658,25 @@ class shading:
             capi.check("vrh_shading_create", ctx.handle, _p(self.materials), len(self.materials),
                        _p(self.lights) if len(self.lights) else None, len(self.lights), C.byref(h))
         self.handle = h
+        self.textures = None
+
+    def set_textures(self, tex_coords, textures):
+        """The tex_coords / textures arguments of make_kernel_params(binding, prims, normals, tex_coords,
+        materials, textures, lights, ...) (kernels.h:396-437): tex_coords (3 * num_prims, 2) float32, three
+        per prim_id; textures one `texture` per material (indexed by geom_id), None = the reference's
+        dummy texture (tex_color 1).  An empty `textures` (or None) detaches them."""
+        textures = list(textures) if textures is not None else []
+        if not textures:
+            capi.check("vrh_shading_set_textures", self.ctx.handle, self.handle, None, 0, None, 0)
+            self.textures = None
+            return
+        tc = np.ascontiguousarray(tex_coords, np.float32).reshape(-1, 2)
+        descs = (capi.vrh_texture_desc * len(textures))()
+        for d, t in zip(descs, textures):
+            if t is not None:
+                t._fill(d)
+        capi.check("vrh_shading_set_textures", self.ctx.handle, self.handle, _p(tc), len(tc), descs, len(textures))
+        self.textures = textures
 
     def close(self):
         if self.handle:
@@ -669,6 +688,73 @@ class shading:
             self.close()
         except Exception:
             pass
+
+
+class tex_filter:
+    nearest, linear = capi.VRH_TEX_NEAREST, capi.VRH_TEX_LINEAR
+
+
+class tex_address:
+    wrap, mirror, clamp = capi.VRH_TEX_WRAP, capi.VRH_TEX_MIRROR, capi.VRH_TEX_CLAMP
+
+
+class texture:
+    """A 2-D texture of 8-bit texels <- texture<vector<4, unorm<8>>, 2> (src/common/model.h:29): `pixels` an
+    (H, W), (H, W, 1), (H, W, 3) or (H, W, 4) uint8 array (rows in order; grey and RGB are expanded with
+    alpha 255 as swizzle.h does), `filter` a tex_filter, `address` a tex_address or a pair (x, y)."""
+
+    def __init__(self, pixels, filter=tex_filter.linear, address=tex_address.wrap):
+        px = np.asarray(pixels)
+        if px.dtype != np.uint8 or px.ndim not in (2, 3):
+            raise TypeError("texture: an (H, W[, C]) uint8 array")
+        if px.ndim == 2:
+            px = px[:, :, None]
+        fmt = {1: capi.VRH_TEX_R8, 3: capi.VRH_TEX_RGB8, 4: capi.VRH_TEX_RGBA8}.get(px.shape[2])
+        if fmt is None:
+            raise TypeError("texture: 1, 3 or 4 channels")
+        self.pixels = np.ascontiguousarray(px)
+        self.format = fmt
+        self.filter = int(filter)
+        self.address = (int(address), int(address)) if np.isscalar(address) else (int(address[0]), int(address[1]))
+
+    @property
+    def width(self):
+        return self.pixels.shape[1]
+
+    @property
+    def height(self):
+        return self.pixels.shape[0]
+
+    def _fill(self, d):
+        d.pixels = self.pixels.ctypes.data if self.pixels.size else None
+        d.width, d.height, d.format, d.filter = self.width, self.height, self.format, self.filter
+        d.address[0], d.address[1] = self.address
+
+    def desc(self):
+        d = capi.vrh_texture_desc()
+        self._fill(d)
+        return d
+
+    def tex2d(self, coords):
+        """tex2D of the reference at (n, 2) coordinates on the host (vrh_tex2d_host): (n, 4) uint8, the
+        sample before its normalisation"""
+        c = np.ascontiguousarray(coords, np.float32).reshape(-1, 2)
+        out = np.zeros((len(c), 4), np.uint8)
+        d = self.desc()
+        capi.check("vrh_tex2d_host", C.byref(d), _p(c), len(c), _p(out))
+        return out
+
+
+def load_pnm(path):
+    """A binary PNM file (P5 / P6, 8-bit samples) as an (H, W, C) uint8 array, C = 1 or 3 (vrh_pnm_load)."""
+    img = capi.vrh_pnm_image()
+    capi.check("vrh_pnm_load", str(path).encode(), C.byref(img))
+    try:
+        n = img.width * img.height * img.channels
+        buf = (C.c_uint8 * n).from_address(img.pixels)
+        return np.frombuffer(buf, np.uint8).reshape(img.height, img.width, img.channels).copy()
+    finally:
+        capi.lib().vrh_pnm_free(C.byref(img))
 
 
 def generic_shading(ctx, materials, lights=()):
@@ -694,6 +780,32 @@ class model:
     def has_vertex_normals(self):
         return len(self.shading_normals) == 3 * len(self.primitives) and len(self.primitives) > 0
 
+    def load_textures(self):
+        """One `texture` (Wrap / Linear, obj_loader.cpp:394-396) or None per material, from the materials'
+        map_Kd paths: resolved relative to the OBJ's directory with backslashes replaced
+        (obj_loader.cpp:377-383; an absolute path that exists is taken as it is).  What load_pnm cannot read
+        -- a missing file, another image format -- is left as the dummy (None) with a warning, as the
+        reference prints one and goes on.  A map shared by several materials is loaded once."""
+        import os
+        import warnings
+
+        loaded, out = {}, []
+        for name in self.textures:
+            if not name:
+                out.append(None)
+                continue
+            if name not in loaded:
+                path = name
+                if not (os.path.isabs(path) and os.path.exists(path)):
+                    path = (os.path.dirname(self.filename) + "/" + name).replace("\\", "/")
+                try:
+                    loaded[name] = texture(load_pnm(path), tex_filter.linear, tex_address.wrap)
+                except capi.VrhError as e:
+                    warnings.warn(f"load_textures: {name}: {e}")
+                    loaded[name] = None
+            out.append(loaded[name])
+        return out
+
 
 def load_obj(filename):
     """load_obj(filename, model&) (src/common/obj_loader.cpp:299-527) through libvrh's parser."""
@@ -703,6 +815,7 @@ def load_obj(filename):
         info = capi.vrh_obj_info()
         capi.check("vrh_obj_get_info", h, C.byref(info))
         m = model()
+        m.filename = str(filename)
         m.primitives = np.zeros(info.num_triangles, TRIANGLE_DTYPE)
         m.geometric_normals = np.zeros((info.num_triangles, 4), np.float32)
         m.shading_normals = np.zeros((info.num_shading_normals, 4), np.float32)

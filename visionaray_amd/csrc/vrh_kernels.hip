@@ -635,8 +635,10 @@ __device__ __forceinline__ uint32_t kernarg_root()
 // BATCH: the same code, instantiated separately for launches of several frames (vrh_render_batch,
 // frames in flight) so that profiles tell them apart from one-frame launches (hip_sched::frame).
 // SPILL: the traversal stack may continue in the global overflow block (stack_t<true>).
+// TEX: the shading samples its diffuse maps at every surface it sets up (vrh_shading_set_textures; vrh_shade.h
+// surface_tex): EPI 1, 3, 4, 5.  The untextured instances are the same code as before the argument existed.
 template <int KIND, bool AO, bool COUNT, int OCC, int EPI = 0, bool LIST = false, bool BATCH = false, bool SPILL = false,
-          bool SAMPLED = false, bool SHARE = false>
+          bool SAMPLED = false, bool SHARE = false, bool TEX = false>
 __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params P)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
@@ -671,6 +673,7 @@ __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params 
     uint32_t bk = 0, res_prim = 0;                 // LIST: the ray's current BVH, merged result
     float res_t = FMAX;
     static_assert(!LIST || EPI == 0, "BVH lists: primary and AO kernels");
+    static_assert(!TEX || EPI == 1 || EPI == 3 || EPI == 4 || EPI == 5, "textures: simple, whitted and path tracing");
 
     if constexpr (!AO)
     {
@@ -687,6 +690,7 @@ __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params 
         mh.n = EPI == 2 ? P.max_hits : 1u;
         whitted_lane w;
         w.shadow = 0; w.depth = 0;
+        uint32_t wtex = TEX_ONE;                   // EPI 3, TEX: the bounce's packed texture sample
         w.sm = reinterpret_cast<float*>(smem); w.base = P.stack_cap * block + tid; w.stride = block;   // EPI 3 LDS words
         pt_lane pt;
         pt.dst = mk3(1.0f, 1.0f, 1.0f); pt.x = 1u; pt.bounce = 0;
@@ -777,14 +781,18 @@ __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params 
                                 if (hit && w.thr > P.eps && w.depth < P.num_bounces)
                                 {
                                     w.depth += 1u;
-                                    whitted_surface(P.shade, P.prims, P.normals, w, r, best_t, best_prim, hx);
+                                    if constexpr (TEX) whitted_surface<true>(P.shade, P.prims, P.normals, w, r, best_t, best_prim, hx, &wtex);
+                                    else whitted_surface(P.shade, P.prims, P.normals, w, r, best_t, best_prim, hx);
                                 }
                                 else
                                     done = 1;
                             }
                         }
                         else
-                            whitted_light_done(P.shade, w, rc > 0);
+                        {
+                            if constexpr (TEX) whitted_light_done<true>(P.shade, w, rc > 0, wtex);
+                            else whitted_light_done(P.shade, w, rc > 0);
+                        }
                         if (mode != IDLE && !done)
                         {
                             if (w.li < P.shade.num_lights)
@@ -853,7 +861,7 @@ __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params 
                             lit = P.num_bounces != 0u;
                             if constexpr (EPI == 5)
                             {
-                                if (lit) pt_last_generic(P.shade, P.prims, pt, hx.li);
+                                if (lit) pt_last_generic<TEX>(P.shade, P.prims, pt, hx.li, best_prim, hx.u, hx.v);
                             }
                             else
                                 pt.dst = mk3(0.0f, 0.0f, 0.0f);
@@ -862,9 +870,9 @@ __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params 
                         {
                             lit = true;
                             if constexpr (EPI == 5)
-                                done = !pt_bounce_generic(P.shade, P.prims, P.normals, pt, r, best_t, best_prim, hx, P.eps);
+                                done = !pt_bounce_generic<TEX>(P.shade, P.prims, P.normals, pt, r, best_t, best_prim, hx, P.eps);
                             else
-                                done = !pt_bounce(P.shade, P.prims, P.normals, pt, r, best_t, best_prim, hx, P.eps);
+                                done = !pt_bounce<TEX>(P.shade, P.prims, P.normals, pt, r, best_t, best_prim, hx, P.eps);
                         }
                         if (!done)
                         {
@@ -902,7 +910,7 @@ __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params 
                     hits_total += hit ? 1 : 0;
                     float4 c = hit ? make_float4(1.0f, 1.0f, 1.0f, 1.0f) : make_float4(P.bg[0], P.bg[1], P.bg[2], P.bg[3]);
                     if constexpr (EPI == 1)
-                        if (hit) c = shade_simple(P.shade, P.prims, P.normals, r, best_t, best_prim, hx);
+                        if (hit) c = shade_simple<TEX>(P.shade, P.prims, P.normals, r, best_t, best_prim, hx);
                     if constexpr (EPI == 2)
                         c = shade_multi(P.shade, P.prims, P.normals, r, mh);
                     if (P.color) put_color<SAMPLED>(P, out_o, c);
@@ -1281,26 +1289,28 @@ __global__ void pack_code_kernel(const uint32_t* __restrict__ pid, const uint8_t
 using kernel_fn = void (*)(render_params);
 
 // the instance of key_at(I), named here and nowhere else: null where instance_exists says there is none
-template <size_t I>
+// (TEX: the textured instance of the key, where textured_instance_exists says there is one)
+template <size_t I, bool TEX>
 static kernel_fn instance_at()
 {
     constexpr instance_key k = key_at(I);
-    if constexpr (instance_exists(k))
-        return dev::render_unified_kernel<k.kind, k.ao, k.count, k.occ, int(k.epi), k.list, k.batch, k.spill, k.sampled, k.share>;
+    if constexpr (TEX ? textured_instance_exists(k) : instance_exists(k))
+        return dev::render_unified_kernel<k.kind, k.ao, k.count, k.occ, int(k.epi), k.list, k.batch, k.spill, k.sampled, k.share, TEX>;
     else
         return nullptr;
 }
 
-template <size_t... I>
+template <bool TEX, size_t... I>
 static kernel_fn find_instance(size_t i, std::index_sequence<I...>)
 {
-    static const kernel_fn table[NUM_KEYS + 1] = { instance_at<I>()..., nullptr };
+    static const kernel_fn table[NUM_KEYS + 1] = { instance_at<I, TEX>()..., nullptr };
     return table[i];
 }
 
-static kernel_fn select_variant(const instance_key& k)
+static kernel_fn select_variant(const launch_config& c)
 {
-    return find_instance(key_index(k), std::make_index_sequence<NUM_KEYS>{});
+    return c.textured ? find_instance<true>(key_index(c), std::make_index_sequence<NUM_KEYS>{})
+                      : find_instance<false>(key_index(c), std::make_index_sequence<NUM_KEYS>{});
 }
 
 size_t render_lds_bytes(const launch_config& c)

@@ -75,6 +75,19 @@ constexpr bool instance_exists(const instance_key& k)
     return !(k.batch && k.count);
 }
 
+// "Textured" is a second axis next to the key (render_unified_kernel's defaulted TEX argument): the
+// instances that sample the shading's diffuse maps (vrh_shading_set_textures).  They exist for the simple,
+// whitted and path-tracing epilogues in the launch forms each has -- one frame; the path tracer also
+// frames in flight and the pixel-sampler pass -- without test counting, and uncapped (occ 1) only: capped at
+// their families' 5 waves / SIMD the whitted and path-tracing ones spill 4-12 VGPRs (12-52 bytes of scratch
+// per lane, -Rpass-analysis=kernel-resource-usage); uncapped they take 103-112 VGPRs (4 waves / SIMD) with
+// no VGPR spill, so a textured launch runs at that lower budget whatever VRH_OPT_WAVES_PER_SIMD asks for.
+constexpr bool textured_instance_exists(const instance_key& k)
+{
+    if (!instance_exists(k) || k.count) return false;
+    return (k.epi == EPI_SIMPLE || k.epi == EPI_WHITTED || k.epi == EPI_PATH || k.epi == EPI_PATH_GENERIC) && k.occ == 1;
+}
+
 // the key domain as a mixed-radix index (vrh_kernels.hip builds its table of instances over it)
 constexpr int KEY_OCCS[4] = { 1, 5, 6, 8 };
 constexpr size_t NUM_KEYS = 2 * 2 * 2 * 4 * 6 * 32;
@@ -103,6 +116,7 @@ struct launch_config : instance_key
     int block;         // threads per block (multiple of 64)
     int stack_cap;     // LDS stack entries per lane
     int max_hits;      // MULTI_HIT: N (LDS hit lists)
+    bool textured;     // the TEX instance of the key (textured_instance_exists)
 };
 
 // dynamic LDS of a launch; `ao_wave_words` (the per-wave AO area) and `whitted_lane_words` (the
@@ -130,6 +144,7 @@ struct launch_inputs
     uint32_t max_hits = 0;                  // VRH_KERNEL_MULTI_HIT: N
     bool generic_shading = false;           // the shading holds tagged material records
     bool sampler_pass = false, hit_mask = false;     // vrh_render_sampled / vrh_render_view; vrh_kernel_desc::hit_mask
+    bool textured = false;                  // the shading has textures attached (vrh_shading_set_textures)
     uint32_t num_frames = 1;
     // the scene: vrh_scene_info and what the upload found (root_is_pair0: roots[0] == 0)
     uint32_t prim_kind = VRH_PRIM_TRI64, max_depth = 1, num_roots = 1;
@@ -165,6 +180,19 @@ constexpr int family_occ(instance_key k, int want)
     {
         k.occ = KEY_OCCS[i];
         if (!instance_exists(k)) continue;
+        least = k.occ;
+        if (below == 0 && k.occ <= want) below = k.occ;
+    }
+    return below ? below : least;
+}
+// the same among the textured instances of the family of `k` (0: it has none)
+constexpr int textured_family_occ(instance_key k, int want)
+{
+    int below = 0, least = 0;
+    for (int i = 3; i >= 0; --i)
+    {
+        k.occ = KEY_OCCS[i];
+        if (!textured_instance_exists(k)) continue;
         least = k.occ;
         if (below == 0 && k.occ <= want) below = k.occ;
     }
@@ -233,6 +261,19 @@ inline int plan_launch(const launch_inputs& in, const launch_device& dev, launch
     const int occ_default = path ? PATH_OCC : whitted ? 5 : lc.epi ? 1 : lc.ao ? occ_ao : occ_primary;
     // sampler passes, BVH lists and the path tracer have instances at some budgets only: the nearest one
     lc.occ = family_occ(lc, opt.occ ? opt.occ : occ_default);
+    if (in.textured)
+    {
+        // a textured shading runs the TEX instance of its key: at the nearest register budget that has one
+        lc.textured = true;
+        lc.occ = textured_family_occ(lc, opt.occ ? opt.occ : occ_default);
+        if (!textured_instance_exists(lc))
+        {
+            err = multi ? "vrh_render: multi_hit takes no textures"
+                : lc.count ? "vrh_render: a textured shading has no test-counting instance"
+                           : "vrh_render: no textured instance of this kernel";
+            return VRH_ERR_UNSUPPORTED;
+        }
+    }
     // AO tail sharing needs several waves per block (they share LDS): 4 unless the block is set.
     // It has instances for uncounted one-frame AO launches at 5 waves / SIMD only: where there is no
     // SHARE instance the option changes nothing, not even the block size

@@ -98,6 +98,15 @@ struct vrh_shading
     vrh::dev::material_t* gmaterials = nullptr;    // tagged records (vrh_shading_create_generic): path tracer only
     vrh::dev::point_light_t* lights = nullptr;
     uint32_t num_materials = 0, num_lights = 0;
+    // the material records sit dev::TEX_BLOCK_BYTES into their allocation `block`: the bytes before them
+    // are the dev::tex_block the textured instances read (vrh_shade.h surface_tex)
+    void* block = nullptr;
+    // vrh_shading_set_textures: texture coordinates (3 per prim_id), one descriptor per material, and the
+    // texel arrays the descriptors point into (descriptors that share pixels share one)
+    float2* tex_coords = nullptr;
+    vrh::dev::tex_view* tex_views = nullptr;
+    std::vector<void*> tex_pixels;
+    uint32_t num_tex_coords = 0, num_textures = 0;
 };
 
 struct vrh_hit_mask

@@ -9,6 +9,7 @@
 #include "vrh_kernels.h"
 #include "vrh_plan.h"
 #include "vrh_lbvh.h"
+#include "vrh_texhost.h"
 
 #include <hip/hip_runtime.h>
 
@@ -712,6 +713,98 @@ VRH_API int vrh_scene_set_vertex_normals(vrh_scene* sc, const void* normals, uin
     return VRH_OK;
 }
 
+// the device block of a shading's material records: dev::TEX_BLOCK_BYTES of zeros (no textures), then
+// `bytes` for the records
+static hipError_t alloc_material_block(vrh_shading* sh, size_t bytes)
+{
+    static_assert(sizeof(dev::tex_block) <= dev::TEX_BLOCK_BYTES && dev::TEX_BLOCK_BYTES % 16 == 0, "texture block");
+    hipError_t e = hipMalloc(&sh->block, dev::TEX_BLOCK_BYTES + bytes);
+    if (e == hipSuccess) e = hipMemset(sh->block, 0, dev::TEX_BLOCK_BYTES);
+    return e;
+}
+
+static void free_textures(vrh_shading* sh)
+{
+    if (sh->tex_coords) (void)hipFree(sh->tex_coords);
+    if (sh->tex_views) (void)hipFree(sh->tex_views);
+    for (void* p : sh->tex_pixels) (void)hipFree(p);
+    sh->tex_coords = nullptr; sh->tex_views = nullptr; sh->tex_pixels.clear();
+    sh->num_tex_coords = 0; sh->num_textures = 0;
+}
+
+VRH_API int vrh_shading_set_textures(vrh_ctx* ctx, vrh_shading* sh, const float* tex_coords, uint32_t num_tex_coords,
+                                     const vrh_texture_desc* textures, uint32_t num_textures)
+{
+    VRH_CHECK(ctx && sh, "vrh_shading_set_textures: null argument");
+    VRH_CHECK(sh->ctx == ctx, "vrh_shading_set_textures: shading of another context");
+    if (num_textures)
+    {
+        VRH_CHECK(textures && tex_coords, "vrh_shading_set_textures: null argument");
+        VRH_CHECK(num_textures == sh->num_materials,
+                  "vrh_shading_set_textures: " + std::to_string(num_textures) + " textures for " + std::to_string(sh->num_materials)
+                      + " materials (textures are indexed by geom_id)");
+        VRH_CHECK(num_tex_coords >= 3 && num_tex_coords % 3 == 0, "vrh_shading_set_textures: 3 tex coords per triangle");
+        for (uint32_t i = 0; i < num_textures; ++i)
+        {
+            const std::string bad = check_texture_desc(textures[i]);
+            VRH_CHECK(bad.empty(), "vrh_shading_set_textures: texture " + std::to_string(i) + ": " + bad);
+        }
+        const size_t bc = first_bad_coord(tex_coords, size_t(num_tex_coords) * 2);
+        VRH_CHECK(bc == size_t(num_tex_coords) * 2, "vrh_shading_set_textures: texture coordinate " + std::to_string(bc / 2)
+                                                         + " is not finite or exceeds 2^20 in magnitude");
+    }
+    int rc = select_device(ctx);
+    if (rc) return rc;
+    // no frame still reads the old table
+    VRH_HIP(ctx_join(ctx));
+    VRH_HIP(hipStreamSynchronize(ctx->stream));
+    dev::tex_block tb{ nullptr, nullptr };
+    VRH_HIP(hipMemcpy(sh->block, &tb, sizeof(tb), hipMemcpyHostToDevice));
+    free_textures(sh);
+    if (!num_textures) return VRH_OK;
+    std::vector<dev::tex_view> views(num_textures);
+    std::vector<uint32_t> expanded;
+    hipError_t e = hipMalloc(&sh->tex_coords, sizeof(float2) * num_tex_coords);
+    if (e == hipSuccess) e = hipMemcpy(sh->tex_coords, tex_coords, sizeof(float2) * num_tex_coords, hipMemcpyHostToDevice);
+    for (uint32_t i = 0; i < num_textures && e == hipSuccess; ++i)
+    {
+        const vrh_texture_desc& d = textures[i];
+        const uint32_t* dpix = nullptr;
+        if (!tex_is_dummy(d))
+        {
+            // descriptors that share a pixel pointer, size and format share one upload
+            for (uint32_t j = 0; j < i && !dpix; ++j)
+                if (!tex_is_dummy(textures[j]) && textures[j].pixels == d.pixels && textures[j].width == d.width
+                    && textures[j].height == d.height && textures[j].format == d.format)
+                    dpix = views[j].pixels;
+            if (!dpix)
+            {
+                expand_rgba8(d, expanded);
+                void* p = nullptr;
+                e = hipMalloc(&p, expanded.size() * 4);
+                if (e != hipSuccess) break;
+                sh->tex_pixels.push_back(p);
+                e = hipMemcpy(p, expanded.data(), expanded.size() * 4, hipMemcpyHostToDevice);
+                dpix = static_cast<const uint32_t*>(p);
+            }
+        }
+        views[i] = dev::make_tex_view(dpix, d.width, d.height, d.filter, d.address[0], d.address[1]);
+    }
+    if (e == hipSuccess) e = hipMalloc(&sh->tex_views, sizeof(dev::tex_view) * num_textures);
+    if (e == hipSuccess) e = hipMemcpy(sh->tex_views, views.data(), sizeof(dev::tex_view) * num_textures, hipMemcpyHostToDevice);
+    tb.tc = sh->tex_coords; tb.tex = sh->tex_views;
+    if (e == hipSuccess) e = hipMemcpy(sh->block, &tb, sizeof(tb), hipMemcpyHostToDevice);
+    if (e != hipSuccess)
+    {
+        set_error(std::string("vrh_shading_set_textures: ") + hipGetErrorString(e));
+        free_textures(sh);
+        return e == hipErrorOutOfMemory ? VRH_ERR_OOM : VRH_ERR_HIP;
+    }
+    sh->num_tex_coords = num_tex_coords;
+    sh->num_textures = num_textures;
+    return VRH_OK;
+}
+
 VRH_API int vrh_shading_create(vrh_ctx* ctx, const vrh_plastic* materials, uint32_t num_materials,
                                const vrh_point_light* lights, uint32_t num_lights, vrh_shading** out)
 {
@@ -727,7 +820,8 @@ VRH_API int vrh_shading_create(vrh_ctx* ctx, const vrh_plastic* materials, uint3
     sh->ctx = ctx;
     sh->num_materials = num_materials;
     sh->num_lights = num_lights;
-    hipError_t e = hipMalloc(&sh->materials, sizeof(vrh_plastic) * num_materials);
+    hipError_t e = alloc_material_block(sh, sizeof(vrh_plastic) * num_materials);
+    if (e == hipSuccess) sh->materials = reinterpret_cast<dev::plastic_t*>(static_cast<char*>(sh->block) + dev::TEX_BLOCK_BYTES);
     if (e == hipSuccess) e = hipMemcpy(sh->materials, materials, sizeof(vrh_plastic) * num_materials, hipMemcpyHostToDevice);
     if (e == hipSuccess && num_lights)
     {
@@ -765,7 +859,8 @@ VRH_API int vrh_shading_create_generic(vrh_ctx* ctx, const vrh_material* materia
     sh->ctx = ctx;
     sh->num_materials = num_materials;
     sh->num_lights = num_lights;
-    hipError_t e = hipMalloc(&sh->gmaterials, sizeof(vrh_material) * num_materials);
+    hipError_t e = alloc_material_block(sh, sizeof(vrh_material) * num_materials);
+    if (e == hipSuccess) sh->gmaterials = reinterpret_cast<dev::material_t*>(static_cast<char*>(sh->block) + dev::TEX_BLOCK_BYTES);
     if (e == hipSuccess) e = hipMemcpy(sh->gmaterials, materials, sizeof(vrh_material) * num_materials, hipMemcpyHostToDevice);
     if (e == hipSuccess && num_lights)
     {
@@ -827,8 +922,8 @@ VRH_API int vrh_shading_free(vrh_shading* sh)
 {
     if (!sh) return VRH_OK;
     if (sh->ctx) (void)hipSetDevice(sh->ctx->device);
-    if (sh->materials) (void)hipFree(sh->materials);
-    if (sh->gmaterials) (void)hipFree(sh->gmaterials);
+    free_textures(sh);
+    if (sh->block) (void)hipFree(sh->block);        // the material records live in it
     if (sh->lights) (void)hipFree(sh->lights);
     delete sh;
     return VRH_OK;
@@ -1184,6 +1279,15 @@ int validate_render(vrh_ctx* ctx, const vrh_scene* sc, vrh_rt* rt, const vrh_cam
         VRH_CHECK(k->normal_binding <= VRH_NORMALS_PER_VERTEX, "vrh_render: unknown normal binding");
         if (k->normal_binding == VRH_NORMALS_PER_FACE) VRH_CHECK(sc->normals, "vrh_render: per-face shading needs face normals");
         else VRH_CHECK(sc->vnormals, "vrh_render: per-vertex shading needs vrh_scene_set_vertex_normals");
+        if (k->shading->num_textures)
+        {
+            if (multi) { set_error("vrh_render: multi_hit takes no textured shading"); return VRH_ERR_UNSUPPORTED; }
+            if (k->hit_mask) { set_error("vrh_render: a textured shading together with a hit mask is not supported"); return VRH_ERR_UNSUPPORTED; }
+            VRH_CHECK(uint64_t(k->shading->num_tex_coords) >= 3ull * (uint64_t(sc->info.max_prim_id) + 1),
+                      "vrh_render: the shading has fewer than 3 tex coords per prim_id of the scene");
+            VRH_CHECK(uint64_t(k->shading->num_tex_coords) / 3 >= sc->info.num_prims,
+                      "vrh_render: the scene has more primitives than the shading has tex coord triples");
+        }
     }
     if (ao)
     {
@@ -1229,6 +1333,7 @@ int plan_render(const vrh_ctx* ctx, const vrh_scene* sc, uint32_t num_frames, co
     launch_inputs in;
     in.kernel = k->kind; in.count_tests = (k->flags & VRH_KERNEL_COUNT_TESTS) != 0; in.max_hits = k->max_hits;
     in.generic_shading = k->shading && k->shading->gmaterials;
+    in.textured = k->shading && k->shading->num_textures != 0 && k->kind != VRH_KERNEL_PRIMARY && k->kind != VRH_KERNEL_AO;
     in.sampler_pass = sampler_pass; in.hit_mask = k->hit_mask != nullptr; in.num_frames = num_frames;
     in.prim_kind = sc->info.prim_kind; in.max_depth = sc->info.max_depth; in.num_roots = sc->num_roots;
     in.device_bytes = sc->info.device_bytes;

@@ -12,6 +12,7 @@
 #include "visionaray_hip/detail/vrh_device.h"
 #include "visionaray_hip/detail/vrh_libm.h"
 #include "visionaray_hip/detail/vrh_sampler.h"
+#include "visionaray_hip/detail/vrh_texture.h"
 
 namespace vrh {
 namespace dev {
@@ -43,12 +44,33 @@ struct shade_params
 
 __device__ __forceinline__ f3 neg(f3 a) { return mk3(-a.x, -a.y, -a.z); }
 
-struct surface_t { f3 gn, sn; plastic_t m; uint32_t mi; };
+// Textures (vrh_shading_set_textures; get_surface.h:422-454).  shade_params keeps its layout -- the
+// untextured instances keep their argument offsets -- so the texture table hangs off the shading's device
+// block: the TEX_BLOCK_BYTES before the material records hold the texture coordinates (3 per prim_id) and
+// the texture descriptors (one per material: textures[geom_id]).  Only the TEX instances read it.
+struct tex_block { const float2* tc; const tex_view* tex; };
+constexpr uint32_t TEX_BLOCK_BYTES = 32;
+constexpr uint32_t TEX_ONE = 0xFFFFFFFFu;       // a packed sample of 255s: tex_color 1.0, the dummy texture's
+
+// tex_color of a hit as the packed RGBA8 sample: the descriptor (two 16-byte loads) and the triangle's
+// three coordinates are fetched together, then the texels
+__device__ inline uint32_t surface_tex(const shade_params& S, uint32_t prim_id, uint32_t mi, float u, float v)
+{
+    const tex_block tb = *reinterpret_cast<const tex_block*>(reinterpret_cast<const char*>(S.materials) - TEX_BLOCK_BYTES);
+    const tex_view t = tb.tex[mi];
+    const float2 a = tb.tc[3u * prim_id], b = tb.tc[3u * prim_id + 1u], c = tb.tc[3u * prim_id + 2u];
+    if (!t.pixels) return TEX_ONE;                                     // width or height 0: C(1.0)
+    return tex2d(t, tex_coord_lerp(a.x, b.x, c.x, u, v), tex_coord_lerp(a.y, b.y, c.y, u, v));
+}
+__device__ __forceinline__ f3 tex_rgb(uint32_t p) { return mk3(unorm8(p), unorm8(p >> 8), unorm8(p >> 16)); }
+
+struct surface_t { f3 gn, sn; plastic_t m; uint32_t mi; uint32_t tex; };
 
 // get_surface (get_surface.h:336-376, 576-592) for a triangle hit: normals by binding, material by
 // the primitive's geom_id
 // (GENERIC: the material is left to the caller, which fetches the tagged record by sf.mi)
-template <bool GENERIC = false>
+// (TEX: sf.tex is the packed texture sample at the hit)
+template <bool GENERIC = false, bool TEX = false>
 __device__ inline surface_t get_surface(const shade_params& S, const float4* __restrict__ prims,
                                         const float4* __restrict__ normals, uint32_t prim_id, uint32_t li,
                                         float u, float v)
@@ -58,6 +80,7 @@ __device__ inline surface_t get_surface(const shade_params& S, const float4* __r
     const float4 qb = q[1], qc = q[2];
     sf.mi = __float_as_uint(qc.z);
     if constexpr (!GENERIC) sf.m = S.materials[sf.mi];
+    if constexpr (TEX && !GENERIC) sf.tex = surface_tex(S, prim_id, sf.mi, u, v);
     if (!S.per_vertex)
     {
         const float4 nn = normals[prim_id];                            // get_normal.h:26-37
@@ -80,14 +103,17 @@ __device__ inline surface_t get_surface(const shade_params& S, const float4* __r
 }
 
 // plastic::shade (plastic.inl:21-37) for one point light: pi * (lambertian + blinn) * intensity * ndotl
-__device__ inline f3 plastic_shade(const plastic_t& m, f3 n, f3 wo, f3 pos, const point_light_t& L)
+// (TEX: the diffuse term is tex_color * lambertian.f, plastic.inl:180-183)
+template <bool TEX = false>
+__device__ inline f3 plastic_shade(const plastic_t& m, f3 n, f3 wo, f3 pos, const point_light_t& L, uint32_t tex = TEX_ONE)
 {
     constexpr float PI = 3.14159265358979323846264338328e+00f;      // math.h:240 constants::pi
     constexpr float INV_PI = 3.18309886183790691216444201928e-01f;  // math.h:242 constants::inv_pi
     const f3 lpos = mk3(L.position[0], L.position[1], L.position[2]);
     const f3 wi = normalize(lpos - pos);                                // simple.inl:59
     const float ndotl = tmax(0.0f, dot(n, wi));                        // plastic.inl:29
-    const f3 cd = (mk3(m.cd[0], m.cd[1], m.cd[2]) * m.kd) * INV_PI;    // lambertian::f, brdf.h:36-41
+    f3 cd = (mk3(m.cd[0], m.cd[1], m.cd[2]) * m.kd) * INV_PI;          // lambertian::f, brdf.h:36-41
+    if constexpr (TEX) cd = tex_rgb(tex) * cd;
     // blinn::f, brdf.h:111-122
     const f3 h = normalize(wo + wi);
     const float hdotn = tmax(0.0f, dot(h, n));
@@ -107,19 +133,20 @@ __device__ inline f3 plastic_shade(const plastic_t& m, f3 n, f3 wo, f3 pos, cons
 }
 
 // colour of a closest hit, simple.inl:32-69 (the miss colour is the caller's)
+template <bool TEX = false>
 __device__ inline float4 shade_simple(const shade_params& S, const float4* __restrict__ prims,
                                       const float4* __restrict__ normals, const ray_t& r, float t,
                                       uint32_t prim_id, const hit_extra& hx)
 {
     const f3 pos = r.ori + r.dir * t;                                  // simple.inl:37
-    const surface_t sf = get_surface(S, prims, normals, prim_id, hx.li, hx.u, hx.v);
+    const surface_t sf = get_surface<false, TEX>(S, prims, normals, prim_id, hx.li, hx.u, hx.v);
     // plastic.inl:13-16 ambient() = ca * ka, times from_rgba(ambient_color) (spectrum.inl:375-378)
     const f3 amb = mk3(S.amb[0], S.amb[1], S.amb[2]);
     f3 shaded = (mk3(sf.m.ca[0], sf.m.ca[1], sf.m.ca[2]) * sf.m.ka) * amb;
     const f3 view = neg(r.dir);
     const f3 n = dot(sf.gn, view) < 0.0f ? neg(sf.sn) : sf.sn;       // faceforward, vector.inl:674-681
     for (uint32_t li = 0; li < S.num_lights; ++li)
-        shaded = shaded + plastic_shade(sf.m, n, view, pos, S.lights[li]);   // simple.inl:63
+        shaded = shaded + plastic_shade<TEX>(sf.m, n, view, pos, S.lights[li], sf.tex);   // simple.inl:63
     return make_float4(shaded.x, shaded.y, shaded.z, 1.0f);           // to_rgba
 }
 
@@ -148,13 +175,18 @@ struct whitted_lane
 constexpr uint32_t WL_POS = 0, WL_N = 3, WL_VIEW = 6, WL_SHADED = 9, WL_WORDS = 12;   // LDS words per lane
 
 // loop body up to the light loop (whitted.inl:225-233), for a hit at t of ray r
+// (TEX: *tex receives the bounce's packed texture sample, which every light of the bounce reads while its
+// shadow ray is in flight: one more register of lane state, kept outside whitted_lane so that the
+// untextured instances keep their code)
+template <bool TEX = false>
 __device__ inline void whitted_surface(const shade_params& S, const float4* __restrict__ prims,
                                        const float4* __restrict__ normals, whitted_lane& w, const ray_t& r, float t,
-                                       uint32_t prim_id, const hit_extra& hx)
+                                       uint32_t prim_id, const hit_extra& hx, uint32_t* tex = nullptr)
 {
     w.st3(WL_POS, r.ori + r.dir * t);
-    const surface_t sf = get_surface(S, prims, normals, prim_id, hx.li, hx.u, hx.v);
+    const surface_t sf = get_surface<false, TEX>(S, prims, normals, prim_id, hx.li, hx.u, hx.v);
     w.mi = sf.mi;
+    if constexpr (TEX) *tex = sf.tex;
     const f3 amb = mk3(S.amb[0], S.amb[1], S.amb[2]);
     w.st3(WL_SHADED, (mk3(sf.m.ca[0], sf.m.ca[1], sf.m.ca[2]) * sf.m.ka) * amb);
     const f3 view = neg(r.dir);
@@ -188,10 +220,11 @@ __device__ inline ray_t whitted_shadow_ray(const shade_params& S, const whitted_
 }
 
 // a shadow ray ended: add the light's plastic::shade unless occluded (select(active, clr, 0))
-__device__ inline void whitted_light_done(const shade_params& S, whitted_lane& w, bool occluded)
+template <bool TEX = false>
+__device__ inline void whitted_light_done(const shade_params& S, whitted_lane& w, bool occluded, uint32_t tex = TEX_ONE)
 {
     const f3 c = occluded ? mk3(0.0f, 0.0f, 0.0f)
-               : plastic_shade(S.materials[w.mi], w.ld3(WL_N), w.ld3(WL_VIEW), w.ld3(WL_POS), S.lights[w.li]);
+               : plastic_shade<TEX>(S.materials[w.mi], w.ld3(WL_N), w.ld3(WL_VIEW), w.ld3(WL_POS), S.lights[w.li], tex);
     w.st3(WL_SHADED, w.ld3(WL_SHADED) + c);
     w.li += 1u;
 }
@@ -221,6 +254,8 @@ __device__ __forceinline__ void pt_basis(f3 w, f3& u, f3& v)
 // Draw order: u, then the lambertian branch's cosine_sample_hemisphere(next(), next()) takes its
 // SECOND argument first (the reference fixtures are g++ builds: arguments right to left), the blinn
 // branch u1 then u2 (two statements).
+// TEX: plastic::sample of a textured shade record (plastic.inl:62) = tex_color * sample_impl(...).
+template <bool TEX = false>
 __device__ inline bool pt_bounce(const shade_params& S, const float4* __restrict__ prims,
                                  const float4* __restrict__ normals, pt_lane& w, ray_t& r, float t,
                                  uint32_t prim_id, const hit_extra& hx, float eps)
@@ -228,7 +263,7 @@ __device__ inline bool pt_bounce(const shade_params& S, const float4* __restrict
     constexpr float PI = 3.14159265358979323846264338328e+00f;      // math.h:240-242 constants
     constexpr float TWO_PI = 6.28318530717958647692528676656e+00f;
     constexpr float INV_PI = 3.18309886183790691216444201928e-01f;
-    const surface_t sf = get_surface(S, prims, normals, prim_id, hx.li, hx.u, hx.v);
+    const surface_t sf = get_surface<false, TEX>(S, prims, normals, prim_id, hx.li, hx.u, hx.v);
     const plastic_t& m = sf.m;
     const f3 wo = neg(r.dir);
     const f3 n = dot(sf.gn, wo) < 0.0f ? neg(sf.sn) : sf.sn;         // faceforward, vector.inl:674-681
@@ -284,6 +319,7 @@ __device__ inline bool pt_bounce(const shade_params& S, const float4* __restrict
         w.dst = mk3(0.0f, 0.0f, 0.0f);
         return false;
     }
+    if constexpr (TEX) src = tex_rgb(sf.tex) * src;
     src = src * (dot(n, wi) / pdf);
     w.dst = mk3(w.dst.x * src.x, w.dst.y * src.y, w.dst.z * src.z);
     const f3 pos = r.ori + r.dir * t;
@@ -308,7 +344,11 @@ __device__ inline bool pt_bounce(const shade_params& S, const float4* __restrict
 // The last iteration of the loop (bounce == num_bounces - 1) on a hit: its sample reaches the image only
 // through an emissive surface (dst *= ce * ls, the path ended); any other path is still alive after the
 // loop, or was killed by pdf <= 0, and is 0 either way
-__device__ inline void pt_last_generic(const shade_params& S, const float4* __restrict__ prims, pt_lane& w, uint32_t li)
+// TEX: emissive (tex_color * ce) * ls (emissive.inl:89), plastic and matte tex_color * sample_impl(...)
+// (plastic.inl:62, matte.inl:64); the mirror body takes no sample
+template <bool TEX = false>
+__device__ inline void pt_last_generic(const shade_params& S, const float4* __restrict__ prims, pt_lane& w, uint32_t li,
+                                       uint32_t prim_id = 0, float u = 0.0f, float v = 0.0f)
 {
     const uint32_t mi = __float_as_uint(prims[3u * li + 2u].z);
     const float4* mp = reinterpret_cast<const float4*>(S.gmaterials + mi);
@@ -317,6 +357,8 @@ __device__ inline void pt_last_generic(const shade_params& S, const float4* __re
     if (__float_as_uint(q0.x) == MAT_EMISSIVE)
     {
         const float ls = mp[1].x;
+        if constexpr (TEX) src = (tex_rgb(surface_tex(S, prim_id, mi, u, v)) * mk3(q0.y, q0.z, q0.w)) * ls;
+        else
         src = mk3(q0.y, q0.z, q0.w) * ls;
         w.dst = mk3(w.dst.x * src.x, w.dst.y * src.y, w.dst.z * src.z);
     }
@@ -324,6 +366,7 @@ __device__ inline void pt_last_generic(const shade_params& S, const float4* __re
         w.dst = src;
 }
 
+template <bool TEX = false>
 __device__ inline bool pt_bounce_generic(const shade_params& S, const float4* __restrict__ prims,
                                          const float4* __restrict__ normals, pt_lane& w, ray_t& r, float t,
                                          uint32_t prim_id, const hit_extra& hx, float eps)
@@ -335,10 +378,16 @@ __device__ inline bool pt_bounce_generic(const shade_params& S, const float4* __
     // words of the record: q0 = kind p0 p1 p2, q1 = p3..p6, q2 = p7..p10, q3 = p11..p14 (material_t)
     const float4* mp = reinterpret_cast<const float4*>(S.gmaterials + sf.mi);
     const uint32_t kind = __float_as_uint(mp[0].x);
+    // the texture sample of the surface, taken here once for the bodies that read it (not the mirror's)
+    uint32_t tex = TEX_ONE;
+    if constexpr (TEX)
+        if (kind != MAT_MIRROR) tex = surface_tex(S, prim_id, sf.mi, hx.u, hx.v);
     if (kind == MAT_EMISSIVE)
     {
         const float4 q0 = mp[0];
-        const f3 src = mk3(q0.y, q0.z, q0.w) * mp[1].x;               // ce_ * ls_
+        f3 src = mk3(q0.y, q0.z, q0.w);
+        if constexpr (TEX) src = tex_rgb(tex) * src;
+        src = src * mp[1].x;                                          // ce_ * ls_
         w.dst = mk3(w.dst.x * src.x, w.dst.y * src.y, w.dst.z * src.z);
         return false;
     }
@@ -432,6 +481,7 @@ __device__ inline bool pt_bounce_generic(const shade_params& S, const float4* __
         w.dst = mk3(0.0f, 0.0f, 0.0f);
         return false;
     }
+    if constexpr (TEX) src = tex_rgb(tex) * src;                      // mirror: tex is TEX_ONE, x * 1.0f = x
     src = src * (dot(n, wi) / pdf);
     w.dst = mk3(w.dst.x * src.x, w.dst.y * src.y, w.dst.z * src.z);
     const f3 pos = r.ori + r.dir * t;
