@@ -36,6 +36,14 @@
 #define VRH_SORTED_PUSH 1    // the 4-wide any-hit step pushes its other hit entries farthest first (0: in
                              // index order; 1: hf1M +0.7 %, hf10M equal, profiles/r04/ab/sorted_push/)
 #endif
+#ifndef VRH_QUAD_STEP
+#define VRH_QUAD_STEP 5      // the 4-wide any-hit step of the AO kernel, one bit per item (profiles/quad_step/):
+                             // 1: its pushes go to the LDS part of the stack only (a ray without LDS room
+                             //    restarts on the binary records), 2: one branch-free group of three stores
+                             //    (needs 1; off: slower than the guarded pushes it replaces, its selects and
+                             //    stores issue also where no lane of the wave pushes), 4: no tn < FLT_MAX
+                             //    compare where the host checked the radius
+#endif
 #ifndef VRH_PACKED_SLABS
 #define VRH_PACKED_SLABS 0   // 1: slab distances with v_pk_add_f32 / v_pk_mul_f32
 #endif
@@ -218,7 +226,7 @@ struct stack_t
     uint32_t base;        // this lane's column (word offset of entry 0)
     uint32_t used;        // entries in use x stride
     uint32_t stride;      // words between entries = threads per block
-    uint32_t cap_off;     // SPILL: LDS entries x stride (wave-uniform; unused otherwise)
+    uint32_t cap_off;     // SPILL: LDS entries x stride (wave-uniform; otherwise read by room_lds<true> only)
     uint32_t lim_off;     // total entries x stride (LDS + overflow; wave-uniform)
     uint32_t* spill;      // SPILL: this block's overflow block (wave-uniform): the entry at used >= cap_off
                           // lives at word base + used - cap_off of it (addressed as byte offset
@@ -267,6 +275,43 @@ struct stack_t
         else
             mem[base + used] = v;
         used += stride;
+    }
+    // The 4-wide any-hit walk keeps to the LDS part (SPILL = false: the whole stack, and these are room /
+    // push): it asks room_lds() first and restarts on the binary records where that fails, so its pushes
+    // need no test against cap_off and no overflow store.  pop() stays checked: lanes of both walks share it.
+    // COUNTED: a counting instance (SPILL = false) asks for the LDS entries init() was told of -- those of the
+    // uncounted launch it stands for -- and so restarts where that launch does
+    template <bool COUNTED = false>
+    __device__ __forceinline__ bool room_lds(uint32_t k) const { return used + k * stride <= ((SPILL || COUNTED) ? cap_off : lim_off); }
+    __device__ __forceinline__ void push_lds(uint32_t v)
+    {
+#if defined(__HIP_DEVICE_COMPILE__)
+        if constexpr (SPILL) *(lds_word*)uintptr_t(entry_addr()) = v;
+        else
+#endif
+            mem[base + used] = v;
+        used += stride;
+    }
+    // m <= 3 pushes in one branch-free group (room_lds(3) holds): w0, w1, w2 are stored at the next three
+    // entries, of which the first m count -- the words above the new top are never read
+    __device__ __forceinline__ void push_lds3(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t m)
+    {
+#if defined(__HIP_DEVICE_COMPILE__)
+        if constexpr (SPILL)
+        {
+            const uint32_t a = entry_addr();
+            *(lds_word*)uintptr_t(a) = w0;
+            *(lds_word*)uintptr_t(a + stride * 4u) = w1;
+            *(lds_word*)uintptr_t(a + stride * 8u) = w2;
+        }
+        else
+#endif
+        {
+            mem[base + used] = w0;
+            mem[base + used + stride] = w1;
+            mem[base + used + 2u * stride] = w2;
+        }
+        used += m * stride;
     }
     __device__ __forceinline__ uint32_t pop()
     {
@@ -427,7 +472,9 @@ constexpr uint32_t NO_RESUME = 0xFFFFFFFFu;   // ray_step: no descent to resume
 
 // One entry of a 4-wide any-hit record (vrh_quad.cpp): the box test of update_if.h:60-66 with
 // best_t = max() (an any-hit ray has no hit yet while it traverses), hardware min/max (the lane's
-// ray is finite, so the slab distances are never NaN).
+// ray is finite, so the slab distances are never NaN).  FINITE_MAX_T: the caller knows max_t <= FLT_MAX
+// (the AO radius, checked by the host), so tn < max_t implies tn < FLT_MAX and that compare is left out.
+template <bool FINITE_MAX_T = false>
 __device__ __forceinline__ bool quad_entry(float xl, float yl, float zl, float xh, float yh, float zh,
                                            const ray_t& r, float max_t, float& tn)
 {
@@ -435,7 +482,8 @@ __device__ __forceinline__ bool quad_entry(float xl, float yl, float zl, float x
     const float t2x = (xh - r.ori.x) * r.inv.x, t2y = (yh - r.ori.y) * r.inv.y, t2z = (zh - r.ori.z) * r.inv.z;
     tn = __builtin_fmaxf(__builtin_fmaxf(__builtin_fminf(t1x, t2x), __builtin_fminf(t1y, t2y)), __builtin_fminf(t1z, t2z));
     const float tf = __builtin_fminf(__builtin_fminf(__builtin_fmaxf(t1x, t2x), __builtin_fmaxf(t1y, t2y)), __builtin_fmaxf(t1z, t2z));
-    return (tf >= tn) & (tn < FMAX) & (tf >= 0.0f) & (tn < max_t);
+    if constexpr (FINITE_MAX_T) return (tf >= tn) & (tf >= 0.0f) & (tn < max_t);
+    else return (tf >= tn) & (tn < FMAX) & (tf >= 0.0f) & (tn < max_t);
 }
 
 // The leaf of the reference loop (intersect.inl:103-128): every primitive of the leaf `link` in
@@ -516,7 +564,9 @@ __device__ __forceinline__ bool leaf_loop(const float4* __restrict__ prims, uint
 // overflow the stack, the ray restarts on the binary records from `root` (still exact).
 // CAPPED = false: an instance without the descent cap (`resume` is never set, `cap` is ignored): the
 // kernels whose launches never cap a descent keep no per-lane visit counter
-template <int KIND, bool COUNT, bool FAST, bool UV = false, class MultiList = void, bool CAPPED = true, class Stack>
+// QUAD_AO: the AO kernel's call -- the 4-wide rays' max_t is the AO radius, which the host found <= FLT_MAX
+// (render_params::quad_ok), and their pushes keep to the LDS part of the stack (VRH_QUAD_STEP)
+template <int KIND, bool COUNT, bool FAST, bool UV = false, class MultiList = void, bool CAPPED = true, bool QUAD_AO = false, class Stack>
 __device__ __forceinline__ int ray_step(const float4* __restrict__ pairs, const float4* __restrict__ prims,
                                         const float4* __restrict__ quads, uint32_t root, bool& quad,
                                         const ray_t& r, float max_t, bool any, Stack& st,
@@ -552,16 +602,20 @@ __device__ __forceinline__ int ray_step(const float4* __restrict__ pairs, const 
             const uint32_t k0 = __float_as_uint(lk.x), k1 = __float_as_uint(lk.y);
             const uint32_t k2 = __float_as_uint(lk.z), k3 = __float_as_uint(lk.w);
             float d0, d1, d2, d3;
-            const bool h0 = quad_entry(xl.x, yl.x, zl.x, xh.x, yh.x, zh.x, r, max_t, d0) & (k0 != QUAD_NONE);
-            const bool h1 = quad_entry(xl.y, yl.y, zl.y, xh.y, yh.y, zh.y, r, max_t, d1) & (k1 != QUAD_NONE);
-            const bool h2 = quad_entry(xl.z, yl.z, zl.z, xh.z, yh.z, zh.z, r, max_t, d2) & (k2 != QUAD_NONE);
-            const bool h3 = quad_entry(xl.w, yl.w, zl.w, xh.w, yh.w, zh.w, r, max_t, d3) & (k3 != QUAD_NONE);
+            constexpr bool LDS_ONLY = QUAD_AO && (VRH_QUAD_STEP & 1) != 0;      // pushes without the overflow test
+            constexpr bool GROUP = LDS_ONLY && (VRH_QUAD_STEP & 2) != 0;        // ... as one branch-free group
+            constexpr bool FIN = QUAD_AO && (VRH_QUAD_STEP & 4) != 0;           // max_t <= FLT_MAX
+            const bool h0 = quad_entry<FIN>(xl.x, yl.x, zl.x, xh.x, yh.x, zh.x, r, max_t, d0) & (k0 != QUAD_NONE);
+            const bool h1 = quad_entry<FIN>(xl.y, yl.y, zl.y, xh.y, yh.y, zh.y, r, max_t, d1) & (k1 != QUAD_NONE);
+            const bool h2 = quad_entry<FIN>(xl.z, yl.z, zl.z, xh.z, yh.z, zh.z, r, max_t, d2) & (k2 != QUAD_NONE);
+            const bool h3 = quad_entry<FIN>(xl.w, yl.w, zl.w, xh.w, yh.w, zh.w, r, max_t, d3) & (k3 != QUAD_NONE);
             if (COUNT) cnt.box += 4;
             if (!(h0 | h1 | h2 | h3)) return st.empty() ? -1 : 0;
-            if (!st.room(3u))
+            auto push = [&](uint32_t v) { if constexpr (LDS_ONLY) st.push_lds(v); else st.push(v); };
+            if (LDS_ONLY ? !st.template room_lds<COUNT>(3u) : !st.room(3u))
             {
                 st.reset();
-                st.push(root);
+                push(root);
                 quad = false;
                 return 0;
             }
@@ -582,18 +636,29 @@ __device__ __forceinline__ int ray_step(const float4* __restrict__ pairs, const 
                 const uint32_t u = sw ? kb : ka; kb = sw ? ka : kb; ka = u;
             };
             cx(e0, c0, e1, c1); cx(e2, c2, e3, c3); cx(e0, c0, e2, c2); cx(e1, c1, e3, c3); cx(e1, c1, e2, c2);
-            if (e3 != INFINITY) st.push(c3);
-            if (e2 != INFINITY) st.push(c2);
-            if (e1 != INFINITY) st.push(c1);
+            if constexpr (GROUP)
+            {
+                // the hit entries are a prefix e1..em of the sorted ones: the same stack content as the
+                // three guarded pushes below, without a branch (the words above the new top are not read)
+                const bool p2 = e2 != INFINITY, p3 = e3 != INFINITY;
+                const uint32_t m = uint32_t(e1 != INFINITY) + uint32_t(p2) + uint32_t(p3);
+                st.push_lds3(p3 ? c3 : p2 ? c2 : c1, p3 ? c2 : c1, c1, m);
+            }
+            else
+            {
+                if (e3 != INFINITY) push(c3);
+                if (e2 != INFINITY) push(c2);
+                if (e1 != INFINITY) push(c1);
+            }
             link = c0;
 #else
             const bool a01 = d1 < d0, a23 = d3 < d2;
             const float m01 = a01 ? d1 : d0, m23 = a23 ? d3 : d2;
             const uint32_t j = (m23 < m01) ? (a23 ? 3u : 2u) : (a01 ? 1u : 0u);
-            if (h0 & (j != 0u)) st.push(k0);
-            if (h1 & (j != 1u)) st.push(k1);
-            if (h2 & (j != 2u)) st.push(k2);
-            if (h3 & (j != 3u)) st.push(k3);
+            if (h0 & (j != 0u)) push(k0);
+            if (h1 & (j != 1u)) push(k1);
+            if (h2 & (j != 2u)) push(k2);
+            if (h3 & (j != 3u)) push(k3);
             link = j == 0u ? k0 : j == 1u ? k1 : j == 2u ? k2 : k3;
 #endif
         }

@@ -33,6 +33,7 @@ struct render_params
     uint32_t fast_ok;         // node bounds all finite: hardware min/max slab path allowed
     const float4* quads;      // 8 float4 per 4-wide any-hit record (vrh_quad.cpp)
     uint32_t quad_ok;         // any-hit rays with finite origin / inverse direction use `quads`
+                              // (AO: only with a radius <= FLT_MAX, fill_params)
 
     frame_camera cam[VRH_MAX_BATCH];   // pinhole basis of every frame of the launch
     uint32_t num_frames;      // frames rendered by this launch (vrh_render_batch)
@@ -86,6 +87,9 @@ struct render_params
                               // (1: entries in cut order, 2: nearest-first)
     uint32_t ao_gate;         // AO step loop: a tile's AO rays are handed out once its primaries are done
     uint32_t ao_share;        // AO step loop, blocks of several waves: tail sharing of the last tiles' AO rays
+    uint32_t quad_lds;        // counting AO instances: the LDS stack entries of the uncounted launch they stand for
+                              // (launch_plan::quad_lds) -- their 4-wide walk restarts where that launch's does
+                              // (in the 4 bytes the pointer below left unused: no other argument moves)
     unsigned long long* wave_times;   // VRH_OPT_WAVE_TIMES: per wave (start, end) of wall_clock64(), else null
     // VRH_OPT_WAVE_TIMES = 2, counting kernels of one-frame AO launches: per tile (hand-out, primaries
     // done, pixels written) of wall_clock64() -- where a launch's tail comes from

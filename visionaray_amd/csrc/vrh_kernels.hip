@@ -649,7 +649,9 @@ __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params 
 
     stack_t<SPILL> st;
     // the overflow entries of this block: (stack_total - stack_cap) entries per lane, same column layout
-    st.init(smem, tid, block, P.stack_cap, SPILL ? P.stack_total : P.stack_cap,
+    // (a counting AO instance holds the whole stack in LDS; its 4-wide walk keeps to the entries the uncounted
+    // launch has there, P.quad_lds, so that it restarts, and counts, as that launch does)
+    st.init(smem, tid, block, (COUNT && AO) ? P.quad_lds : P.stack_cap, SPILL ? P.stack_total : P.stack_cap,
             SPILL ? P.stack_spill + size_t(blockIdx.x) * (P.stack_total - P.stack_cap) * block : nullptr);
     uint32_t* ao_area = smem + P.stack_cap * block + wave * AO_WAVE_WORDS;
     test_counts cnt = {};
@@ -997,7 +999,14 @@ __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params 
                     tn = __builtin_fmaxf(tn, __builtin_fminf(t1, t2)); tf = __builtin_fminf(tf, __builtin_fmaxf(t1, t2));
                     t1 = (e[2] - r.ori.z) * r.inv.z; t2 = (e[5] - r.ori.z) * r.inv.z;
                     tn = __builtin_fmaxf(tn, __builtin_fminf(t1, t2)); tf = __builtin_fminf(tf, __builtin_fmaxf(t1, t2));
-                    if ((tf >= tn) & (tn < FMAX) & (tf >= 0.0f) & (tn < max_t)) st.push(__float_as_uint(e[6]));
+                    // (VRH_QUAD_STEP: push_lds is unchecked.  Invariant: the stack is empty and cutn + 4 <= the
+                    // LDS entries -- every cutn that reaches here, this wave's cutN or a sibling's SH_CUTN, is
+                    // the value the cut build clamped to NONE otherwise, and all waves of a block share one
+                    // capacity.  A 4-wide ray's radius is <= FLT_MAX (plan_launch: quad_ok), so tn < max_t
+                    // implies tn < FMAX)
+                    const bool pass = (VRH_QUAD_STEP & 4) ? (tf >= tn) & (tf >= 0.0f) & (tn < max_t)
+                                                          : (tf >= tn) & (tn < FMAX) & (tf >= 0.0f) & (tn < max_t);
+                    if (pass) { if constexpr ((VRH_QUAD_STEP & 1) != 0) st.push_lds(__float_as_uint(e[6])); else st.push(__float_as_uint(e[6])); }
                 }
                 if (COUNT) cnt.box += cutn;
             }
@@ -1085,7 +1094,7 @@ __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params 
                     {
                         // the tile's first AO hand-out: all its hits are published (ao_gate)
                         cutN = uu(ao_cut_build<COUNT>(P, recs, pubC, cut, lane, cnt));   // wave-uniform (SGPR)
-                        if (cutN != NONE && cutN + 4u > P.stack_cap) cutN = NONE;
+                        if (cutN != NONE && cutN + 4u > (COUNT ? P.quad_lds : P.stack_cap)) cutN = NONE;
                     }
                 // once the block's queues are dry, the tile's AO rays are handed out through the LDS
                 // counter of its header, which idle sibling waves claim from too (step 3b)
@@ -1191,11 +1200,13 @@ __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params 
                 // the AO kernel's rays: any-hit AO rays up to the radius, closest-hit primaries unbounded
                 // (derived from `any` instead of a per-lane max_t).  The root link ray_step restarts a
                 // 4-wide descent at is pair 0: 4-wide records exist only for trees whose root is a pair,
-                // stored first (render_params::quad_ok checks it), so no register holds it
+                // stored first (render_params::quad_ok checks it), so no register holds it.  QUAD_AO: a
+                // 4-wide ray here is an AO ray, its max_t the radius that quad_ok found <= FLT_MAX (a list
+                // of BVHs has no 4-wide records: its instances keep the plain call)
                 const float mt = VRH_AO_LEAN ? (any ? P.radius : FMAX) : max_t;
                 rc = (P.fast_ok && __ballot((tag & TAG_NONFINITE) != 0u) == 0ull)
-                    ? ray_step<KIND, COUNT, true, false, void, AO_CAPPED>(P.pairs, P.prims, P.quads, 0u, quad, r, mt, any, st, best_t, best_prim, cnt, steps, P.step_limit, resume, P.descent_cap, P.step_flags, nullptr, static_cast<const void*>(nullptr), hm)
-                    : ray_step<KIND, COUNT, false, false, void, AO_CAPPED>(P.pairs, P.prims, P.quads, 0u, quad, r, mt, any, st, best_t, best_prim, cnt, steps, P.step_limit, resume, P.descent_cap, P.step_flags, nullptr, static_cast<const void*>(nullptr), hm);
+                    ? ray_step<KIND, COUNT, true, false, void, AO_CAPPED, !LIST>(P.pairs, P.prims, P.quads, 0u, quad, r, mt, any, st, best_t, best_prim, cnt, steps, P.step_limit, resume, P.descent_cap, P.step_flags, nullptr, static_cast<const void*>(nullptr), hm)
+                    : ray_step<KIND, COUNT, false, false, void, AO_CAPPED, !LIST>(P.pairs, P.prims, P.quads, 0u, quad, r, mt, any, st, best_t, best_prim, cnt, steps, P.step_limit, resume, P.descent_cap, P.step_flags, nullptr, static_cast<const void*>(nullptr), hm);
             }
             if constexpr (LIST)
                 if (busy && rc < 0) rc = list_next(P, any, bk, res_t, res_prim, best_t, best_prim, st, resume);

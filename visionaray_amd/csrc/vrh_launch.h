@@ -150,6 +150,7 @@ struct launch_inputs
     uint32_t prim_kind = VRH_PRIM_TRI64, max_depth = 1, num_roots = 1;
     uint64_t device_bytes = 0;
     bool finite_bounds = true, has_quads = false, root_is_pair0 = true;
+    bool radius_finite = true;              // AO: the radius is <= FLT_MAX (the 4-wide step's test relies on it)
     tuning_options opt;
 };
 
@@ -166,6 +167,9 @@ struct launch_plan
     launch_config cfg;
     uint32_t stack_total;     // stack entries per lane in all: cfg.stack_cap in LDS, the rest in the overflow block
     int per_cu;               // blocks per CU the grid is sized for
+    uint32_t quad_lds;        // stack entries the AO kernel's 4-wide any-hit walk keeps to (it restarts on the binary
+                              // records beyond them): cfg.stack_cap; a counting launch, whose instance holds the
+                              // whole stack in LDS, takes the uncounted launch's, so that it counts that launch's tests
     // render_params fields of the same names
     uint32_t refill_min, refill_min_primary, descent_cap, step_flags, ao_gate, fast_ok, quad_ok, ao_cut, ao_share,
              xcd_queues, cluster;
@@ -306,6 +310,17 @@ inline int plan_launch(const launch_inputs& in, const launch_device& dev, launch
     }
     out.cfg = lc;
     out.stack_total = total;
+    out.quad_lds = uint32_t(lc.stack_cap);
+    if (lc.ao && lc.count)
+    {
+        launch_inputs plain = in;
+        plain.count_tests = false;
+        launch_plan p{};
+        std::string e;
+        // (an uncounted launch that has no plan changes nothing: the counting launch keeps its own LDS entries,
+        // which is what it did before; the error, if any, is this launch's own and was reported above)
+        if (plan_launch(plain, dev, p, e) == VRH_OK) out.quad_lds = std::min(out.quad_lds, uint32_t(p.cfg.stack_cap));
+    }
 
     // measured: profiles/r01/ab (AO: refill at 32 free lanes), profiles/r01/ab_primary (primary
     // visibility: pop on a miss and a cap of 8 visits per descent step, +6 % on hf1M and +36 % on
@@ -340,7 +355,8 @@ inline int plan_launch(const launch_inputs& in, const launch_device& dev, launch
     // 4-wide any-hit records: auto on for the AO step loop (with ao_gate), off elsewhere
     const bool wide = opt.wide == 1 || (opt.wide == 0 && lc.ao);
     // (the AO kernel restarts a 4-wide descent that would overflow its stack at pair 0: the root)
-    out.quad_ok = (in.has_quads && out.fast_ok && wide && in.root_is_pair0) ? 1u : 0u;
+    // (and its 4-wide box test takes tn < radius to imply tn < FLT_MAX: a non-finite AO radius keeps the binary records)
+    out.quad_ok = (in.has_quads && out.fast_ok && wide && in.root_is_pair0 && (!lc.ao || in.radius_finite)) ? 1u : 0u;
     // per-tile entry cut of the 4-wide tree for AO rays (needs the gate: the tile's hits are known)
     // entries nearest-first (+3.5 % over the cut order, profiles/r02_ab/ab33_ao_cut_order*.log)
     out.ao_cut = (out.quad_ok && out.ao_gate && opt.cut != 2) ? (opt.cut == 3 ? 1u : 2u) : 0u;

@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cfloat>
 #include <cmath>
 #include <cstring>
 #include <initializer_list>
@@ -1339,6 +1340,9 @@ int plan_render(const vrh_ctx* ctx, const vrh_scene* sc, uint32_t num_frames, co
     in.device_bytes = sc->info.device_bytes;
     in.finite_bounds = sc->finite_bounds; in.has_quads = sc->quads != nullptr; in.root_is_pair0 = sc->roots[0] == 0u;
     in.opt = ctx->opt;
+    // the AO kernel's 4-wide step leaves out the tn < FLT_MAX compare that tn < radius implies
+    // (VRH_QUAD_STEP & 4): an AO radius that is not <= FLT_MAX (inf, NaN) walks the binary records instead
+    in.radius_finite = !(VRH_QUAD_STEP & 4) || k->kind != VRH_KERNEL_AO || k->radius <= FLT_MAX;
     std::string err;
     const int rc = plan_launch(in, render_device{}, plan, err);
     if (rc) set_error(err);
@@ -1358,7 +1362,7 @@ int fill_params(render_params& p, const launch_plan& plan, const vrh_ctx* ctx, c
     p.step_limit = sc->info.num_nodes + sc->info.num_indices + 16u;
     p.refill_min = plan.refill_min; p.refill_min_primary = plan.refill_min_primary; p.descent_cap = plan.descent_cap;
     p.ao_gate = plan.ao_gate; p.step_flags = plan.step_flags;
-    p.stack_cap = uint32_t(plan.cfg.stack_cap); p.stack_total = plan.stack_total;
+    p.stack_cap = uint32_t(plan.cfg.stack_cap); p.stack_total = plan.stack_total; p.quad_lds = plan.quad_lds;
     p.fast_ok = plan.fast_ok;
     p.quads = sc->quads; p.quad_ok = plan.quad_ok;
     p.ao_cut = plan.ao_cut; p.ao_share = plan.ao_share;
