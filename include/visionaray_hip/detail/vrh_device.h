@@ -28,6 +28,7 @@
 #include <type_traits>
 
 #include "vrh_sampler.h"
+#include "vrh_fused_slab.h"
 
 #ifndef VRH_SCALAR_UNIFORM
 #define VRH_SCALAR_UNIFORM 1   // wave-uniform pair fetches through the scalar cache (ray_step)
@@ -37,12 +38,23 @@
                              // index order; 1: hf1M +0.7 %, hf10M equal, profiles/r04/ab/sorted_push/)
 #endif
 #ifndef VRH_QUAD_STEP
-#define VRH_QUAD_STEP 5      // the 4-wide any-hit step of the AO kernel, one bit per item (profiles/quad_step/):
+#define VRH_QUAD_STEP 5      // the 4-wide any-hit step of the AO kernel, one bit per item (profiles/quad_step/,
+                             // profiles/fused_slab/):
                              // 1: its pushes go to the LDS part of the stack only (a ray without LDS room
                              //    restarts on the binary records), 2: one branch-free group of three stores
                              //    (needs 1; off: slower than the guarded pushes it replaces, its selects and
                              //    stores issue also where no lane of the wave pushes), 4: no tn < FLT_MAX
-                             //    compare where the host checked the radius
+                             //    compare where the host checked the radius, 8: where the scene has the fused
+                             //    records (vrh_fused_slab.h) the rays walk those, one v_fma per slab distance, and
+                             //    a leaf counts only if its exact box passes the exact test (off: with 16 and 32
+                             //    +1.1 % over the parent but -0.9 % against this tree without it, and its mere
+                             //    presence in the kernel costs as much; libvrh_fused.so is the build with 8 + 16
+                             //    + 32 that the tests run), 16: (needs 8) no
+                             //    compare of the fused records' links against QUAD_NONE -- their unused entries
+                             //    are point boxes at +inf, which no finite ray passes, 32: (needs 8) where the
+                             //    exact box is tested: fetched with the leaf's triangles and tested before them
+                             //    (off: fetched through the leaf-slot index and tested only after a hit, whose
+                             //    two dependent loads cost more than the fused test saves: -1 % against +0.8 %)
 #endif
 #ifndef VRH_PACKED_SLABS
 #define VRH_PACKED_SLABS 0   // 1: slab distances with v_pk_add_f32 / v_pk_mul_f32
@@ -359,6 +371,8 @@ struct test_counts
     // AO hand-outs: events (a wave starting AO rays in its idle lanes), rays started, and runs of
     // started rays that share a hit slot (a run's lanes need the same normal and basis)
     uint32_t ho_events, ho_rays, ho_runs;
+    // fused 4-wide records: hits checked against their leaf's exact box, and checks that failed (per lane)
+    uint32_t fz_checks, fz_rejects;
 };
 // kinds of the counted vector-memory instructions
 constexpr uint32_t VMEM_PRIM = 0, VMEM_QUAD = 1, VMEM_PAIR = 2, VMEM_NORMAL = 3, VMEM_STORE = 4;
@@ -492,7 +506,8 @@ __device__ __forceinline__ bool quad_entry(float xl, float yl, float zl, float x
 template <int KIND, bool COUNT, bool UV, class MultiList>
 __device__ __forceinline__ bool leaf_loop(const float4* __restrict__ prims, uint32_t link, const ray_t& r, float max_t,
                                           bool any, float& best_t, uint32_t& best_prim, test_counts& cnt,
-                                          hit_extra* hx, const MultiList* mh, const hit_mask_params* hm)
+                                          hit_extra* hx, const MultiList* mh, const hit_mask_params* hm,
+                                          uint32_t* hit_index = nullptr)
 {
     uint32_t i = link & ~LEAF_BIT;
     for (;;)
@@ -537,7 +552,7 @@ __device__ __forceinline__ bool leaf_loop(const float4* __restrict__ prims, uint
                 best_t = t;
                 best_prim = pid;
                 if constexpr (UV) { hx->u = hu; hx->v = hv; hx->li = i; }   // hit_record.h:54-64
-                if (any) return true;                            // exit_traversal.h:49-56
+                if (any) { if (hit_index) *hit_index = i; return true; }   // exit_traversal.h:49-56
             }
         }
         if (flags & END_BIT) break;
@@ -565,7 +580,12 @@ __device__ __forceinline__ bool leaf_loop(const float4* __restrict__ prims, uint
 // CAPPED = false: an instance without the descent cap (`resume` is never set, `cap` is ignored): the
 // kernels whose launches never cap a descent keep no per-lane visit counter
 // QUAD_AO: the AO kernel's call -- the 4-wide rays' max_t is the AO radius, which the host found <= FLT_MAX
-// (render_params::quad_ok), and their pushes keep to the LDS part of the stack (VRH_QUAD_STEP)
+// (render_params::quad_ok), and their pushes keep to the LDS part of the stack (VRH_QUAD_STEP).  With flags bit 2
+// `quads` are the fused records: the walk reaches a superset of the reference's leaves (the boxes are widened so
+// that the fused test never fails where the exact one passes), and a hit counts only if the exact box of its leaf --
+// entry leaf_slot[primitive] of `exact_quads` -- passes quad_entry; with every box inside its parent's that is
+// equivalent to the reference reaching the leaf, so the result is the reference's.  A rejected leaf is left like
+// one without a hit.
 template <int KIND, bool COUNT, bool FAST, bool UV = false, class MultiList = void, bool CAPPED = true, bool QUAD_AO = false, class Stack>
 __device__ __forceinline__ int ray_step(const float4* __restrict__ pairs, const float4* __restrict__ prims,
                                         const float4* __restrict__ quads, uint32_t root, bool& quad,
@@ -573,8 +593,11 @@ __device__ __forceinline__ int ray_step(const float4* __restrict__ pairs, const 
                                         float& best_t, uint32_t& best_prim, test_counts& cnt,
                                         uint32_t& steps, uint32_t step_limit, uint32_t& resume, uint32_t cap,
                                         uint32_t flags, hit_extra* hx = nullptr, const MultiList* mh = nullptr,
-                                        const hit_mask_params* hm = nullptr)
+                                        const hit_mask_params* hm = nullptr, const float4* __restrict__ exact_quads = nullptr,
+                                        const uint32_t* __restrict__ leaf_slot = nullptr)
 {
+    constexpr bool FUSED = QUAD_AO && (VRH_QUAD_STEP & 8) != 0;
+    const bool fz = FUSED && (flags & 4u) != 0u;       // wave-uniform
     // flags (render_params::step_flags): bit 0 pop on miss, bit 1 scalar fetch of wave-uniform pairs
     const bool pop_on_miss = (flags & 1u) != 0u;
     const bool scalar_uniform = SCALAR_UNIFORM && (flags & 2u) != 0u;
@@ -592,7 +615,10 @@ __device__ __forceinline__ int ray_step(const float4* __restrict__ pairs, const 
         if (++steps > step_limit) { cnt.aborted = true; return -1; }
         link = st.pop();
     }
-    if (quad)
+    // the 4-wide descent to a leaf; FZ: over the fused records (one copy of the loop each, chosen per wave below,
+    // so that neither holds the other's values).  Returns 2 at a leaf, else ray_step's result
+    constexpr int AT_LEAF = 2;
+    auto walk = [&](auto FZ) __attribute__((always_inline)) -> int
     {
         while (!(link & LEAF_BIT))
         {
@@ -605,10 +631,23 @@ __device__ __forceinline__ int ray_step(const float4* __restrict__ pairs, const 
             constexpr bool LDS_ONLY = QUAD_AO && (VRH_QUAD_STEP & 1) != 0;      // pushes without the overflow test
             constexpr bool GROUP = LDS_ONLY && (VRH_QUAD_STEP & 2) != 0;        // ... as one branch-free group
             constexpr bool FIN = QUAD_AO && (VRH_QUAD_STEP & 4) != 0;           // max_t <= FLT_MAX
-            const bool h0 = quad_entry<FIN>(xl.x, yl.x, zl.x, xh.x, yh.x, zh.x, r, max_t, d0) & (k0 != QUAD_NONE);
-            const bool h1 = quad_entry<FIN>(xl.y, yl.y, zl.y, xh.y, yh.y, zh.y, r, max_t, d1) & (k1 != QUAD_NONE);
-            const bool h2 = quad_entry<FIN>(xl.z, yl.z, zl.z, xh.z, yh.z, zh.z, r, max_t, d2) & (k2 != QUAD_NONE);
-            const bool h3 = quad_entry<FIN>(xl.w, yl.w, zl.w, xh.w, yh.w, zh.w, r, max_t, d3) & (k3 != QUAD_NONE);
+            bool h0, h1, h2, h3;
+            if constexpr (decltype(FZ)::value)
+            {
+                constexpr bool INF_UNUSED = (VRH_QUAD_STEP & 16) != 0;
+                const float nx = -(r.ori.x * r.inv.x), ny = -(r.ori.y * r.inv.y), nz = -(r.ori.z * r.inv.z);
+                h0 = fused::entry<FIN>(xl.x, yl.x, zl.x, xh.x, yh.x, zh.x, r.inv.x, r.inv.y, r.inv.z, nx, ny, nz, max_t, d0) & (INF_UNUSED || k0 != QUAD_NONE);
+                h1 = fused::entry<FIN>(xl.y, yl.y, zl.y, xh.y, yh.y, zh.y, r.inv.x, r.inv.y, r.inv.z, nx, ny, nz, max_t, d1) & (INF_UNUSED || k1 != QUAD_NONE);
+                h2 = fused::entry<FIN>(xl.z, yl.z, zl.z, xh.z, yh.z, zh.z, r.inv.x, r.inv.y, r.inv.z, nx, ny, nz, max_t, d2) & (INF_UNUSED || k2 != QUAD_NONE);
+                h3 = fused::entry<FIN>(xl.w, yl.w, zl.w, xh.w, yh.w, zh.w, r.inv.x, r.inv.y, r.inv.z, nx, ny, nz, max_t, d3) & (INF_UNUSED || k3 != QUAD_NONE);
+            }
+            else
+            {
+                h0 = quad_entry<FIN>(xl.x, yl.x, zl.x, xh.x, yh.x, zh.x, r, max_t, d0) & (k0 != QUAD_NONE);
+                h1 = quad_entry<FIN>(xl.y, yl.y, zl.y, xh.y, yh.y, zh.y, r, max_t, d1) & (k1 != QUAD_NONE);
+                h2 = quad_entry<FIN>(xl.z, yl.z, zl.z, xh.z, yh.z, zh.z, r, max_t, d2) & (k2 != QUAD_NONE);
+                h3 = quad_entry<FIN>(xl.w, yl.w, zl.w, xh.w, yh.w, zh.w, r, max_t, d3) & (k3 != QUAD_NONE);
+            }
             if (COUNT) cnt.box += 4;
             if (!(h0 | h1 | h2 | h3)) return st.empty() ? -1 : 0;
             auto push = [&](uint32_t v) { if constexpr (LDS_ONLY) st.push_lds(v); else st.push(v); };
@@ -662,6 +701,12 @@ __device__ __forceinline__ int ray_step(const float4* __restrict__ pairs, const 
             link = j == 0u ? k0 : j == 1u ? k1 : j == 2u ? k2 : k3;
 #endif
         }
+        return AT_LEAF;
+    };
+    if (quad)
+    {
+        const int w = (FUSED && fz) ? walk(std::true_type{}) : walk(std::false_type{});
+        if (w != AT_LEAF) return w;
     }
     else for (uint32_t it = cap; !(link & LEAF_BIT); --it)
     {
@@ -725,7 +770,42 @@ __device__ __forceinline__ int ray_step(const float4* __restrict__ pairs, const 
         }
         link = go0 ? l0 : l1;
     }
-    if (leaf_loop<KIND, COUNT, UV, MultiList>(prims, link, r, max_t, any, best_t, best_prim, cnt, hx, mh, hm)) return 1;
+    if constexpr (FUSED && (VRH_QUAD_STEP & 32) != 0)
+        if (fz && quad)
+        {
+            // placement (a): the leaf's exact box, keyed by its first primitive, is fetched with its triangles and
+            // tested before them -- a leaf the reference does not reach is left at once, no load waits for a hit
+            const float4* lb = reinterpret_cast<const float4*>(leaf_slot) + 2u * (link & ~LEAF_BIT);
+            const float4 lo = lb[0], hi = lb[1];
+            if (COUNT) count_vmem(cnt, lb, 2u, VMEM_QUAD);
+            constexpr bool FIN = (VRH_QUAD_STEP & 4) != 0;
+            float tn;
+            const bool reached = quad_entry<FIN>(lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, r, max_t, tn);
+            if (COUNT) { cnt.fz_checks += 1u; cnt.fz_rejects += reached ? 0u : 1u; }
+            if (!reached) return st.empty() ? -1 : 0;
+        }
+    uint32_t hit_index = 0u;
+    if (leaf_loop<KIND, COUNT, UV, MultiList>(prims, link, r, max_t, any, best_t, best_prim, cnt, hx, mh, hm,
+                                              (FUSED && !(VRH_QUAD_STEP & 32)) ? &hit_index : nullptr))
+    {
+        if constexpr (FUSED && !(VRH_QUAD_STEP & 32))
+            if (fz && quad)
+            {
+                // the hit was found through the widened boxes: it counts only if the reference reaches the leaf
+                const uint32_t slot = leaf_slot[hit_index];
+                const float* q = reinterpret_cast<const float*>(exact_quads) + 32u * (slot >> 2) + (slot & 3u);
+                constexpr bool FIN = (VRH_QUAD_STEP & 4) != 0;
+                float tn;
+                const bool reached = quad_entry<FIN>(q[0], q[4], q[8], q[12], q[16], q[20], r, max_t, tn);
+                if (COUNT) { cnt.fz_checks += 1u; cnt.fz_rejects += reached ? 0u : 1u; }
+                if (!reached)
+                {
+                    best_t = FMAX; best_prim = 0u;
+                    return st.empty() ? -1 : 0;
+                }
+            }
+        return 1;
+    }
     return st.empty() ? -1 : 0;
 }
 

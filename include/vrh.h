@@ -241,7 +241,10 @@ typedef struct {
      * consecutive started rays that share a hit slot (rays / runs = lanes that need the same normal
      * and basis) */
     uint64_t ao_handout_events, ao_handout_rays, ao_handout_slot_runs;
-    uint64_t reserved[9];
+    /* fused 4-wide records: hits found through them that were checked against their leaf's exact box, and
+     * the checks that failed (the leaf is skipped: the reference does not reach it) */
+    uint64_t fused_checks, fused_rejects;
+    uint64_t reserved[7];
 } vrh_handout_stats;
 
 typedef struct {
@@ -256,6 +259,9 @@ typedef struct {
     uint32_t gpu_built;       /* built by vrh_scene_build                                        */
     float    build_ms;        /* vrh_scene_build: device time of the build kernels               */
     uint32_t num_bvhs;        /* BVHs in the scene (> 1: a list, vrh_scene_list_create)          */
+    uint32_t fused_records;   /* 4-wide records over widened boxes for the AO kernel's fused slab test
+                                 (0: none -- no 4-wide records, or a node's box is not inside its parent's) */
+    uint64_t fused_bytes;     /* device bytes they add (the records and the leaf-box index; not in device_bytes) */
 } vrh_scene_info;
 
 /* camera::look_at + camera::perspective (camera.inl:10-57) followed by the pinhole basis that
@@ -366,6 +372,15 @@ enum vrh_option {
                                     depth-first preorder, a pair's child-0 pair next to it in one
                                     128-B line; 2 = the builder's order (auto: 2; 1 measured
                                     neutral)                                                      */
+    VRH_OPT_FUSED_STEP = 28,     /* scene upload (read by vrh_scene_upload), builds with VRH_QUAD_STEP & 8 only
+                                    (libvrh_fused.so; the default build has no fused step and ignores it):
+                                    2 = no fused 4-wide records for this scene, its AO rays take the exact
+                                    4-wide step (auto, 1: records built where the tree nests)               */
+    VRH_OPT_FUSED_WIDEN = 27,    /* scene upload (read by vrh_scene_upload): the boxes of the fused 4-wide
+                                    records are widened by at least the scene extent x 2^-value, 1..30
+                                    (auto, 0: the derived widening alone).  Results
+                                    do not depend on it: a test exaggerates it so that the verification
+                                    of hits against the exact leaf boxes has rejects to show           */
 };
 /* every value is checked against its option's range (the comments above) before it is narrowed:
  * out of range -> VRH_ERR_INVALID, a removed setting -> VRH_ERR_UNSUPPORTED, unknown option ->

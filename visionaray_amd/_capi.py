@@ -68,6 +68,8 @@ VRH_OPT_CLUSTER_TILES = 23
 VRH_OPT_QUAD_REFILL = 24
 VRH_OPT_GROUP_UNITS = 25
 VRH_OPT_ASYNC_FRAMES = 26
+VRH_OPT_FUSED_WIDEN = 27
+VRH_OPT_FUSED_STEP = 28
 VRH_OPT_AO_STEAL = 21
 VRH_MAX_TIMED_FRAMES = 1024
 VRH_MAX_SCENE_LIST = 8
@@ -111,7 +113,8 @@ class vrh_frame_stats(C.Structure):
 class vrh_handout_stats(C.Structure):
     _fields_ = [("ao_handout_ticks", C.c_uint64), ("primary_handout_ticks", C.c_uint64), ("step_ticks", C.c_uint64),
                 ("loop_ticks", C.c_uint64), ("ao_handout_events", C.c_uint64), ("ao_handout_rays", C.c_uint64),
-                ("ao_handout_slot_runs", C.c_uint64), ("reserved", C.c_uint64 * 9)]
+                ("ao_handout_slot_runs", C.c_uint64), ("fused_checks", C.c_uint64), ("fused_rejects", C.c_uint64),
+                ("reserved", C.c_uint64 * 7)]
 
 
 class vrh_scene_view(C.Structure):
@@ -126,7 +129,8 @@ class vrh_scene_info(C.Structure):
                 ("prim_kind", C.c_uint32), ("max_depth", C.c_uint32), ("device_bytes", C.c_uint64),
                 ("wide_records", C.c_uint32), ("wide_depth", C.c_uint32), ("max_prim_id", C.c_uint32),
                 ("max_geom_id", C.c_uint32), ("vertex_normals", C.c_uint32), ("gpu_built", C.c_uint32),
-                ("build_ms", C.c_float), ("num_bvhs", C.c_uint32)]
+                ("build_ms", C.c_float), ("num_bvhs", C.c_uint32), ("fused_records", C.c_uint32),
+                ("fused_bytes", C.c_uint64)]
 
 
 class vrh_build_desc(C.Structure):

@@ -166,7 +166,8 @@ class Context:
                  "pair_layout": capi.VRH_OPT_PAIR_LAYOUT, "ao_gate": capi.VRH_OPT_AO_GATE, "ao_cut": capi.VRH_OPT_AO_CUT, "wave_times": capi.VRH_OPT_WAVE_TIMES,
                  "ao_share": capi.VRH_OPT_AO_SHARE, "cluster_tiles": capi.VRH_OPT_CLUSTER_TILES,
                  "quad_refill": capi.VRH_OPT_QUAD_REFILL, "group_units": capi.VRH_OPT_GROUP_UNITS,
-                 "async_frames": capi.VRH_OPT_ASYNC_FRAMES}
+                 "async_frames": capi.VRH_OPT_ASYNC_FRAMES, "fused_widen": capi.VRH_OPT_FUSED_WIDEN,
+                 "fused_step": capi.VRH_OPT_FUSED_STEP}
         opt = names.get(option, option)
         capi.check("vrh_ctx_set_option", self.handle, opt, int(value))
         if opt == capi.VRH_OPT_ASYNC_FRAMES:

@@ -39,8 +39,20 @@ constexpr uint32_t QUAD_NONE = 0xFFFFFFFFu;     // unused entry of a 4-wide reco
 
 // 4-wide any-hit records from the binary BVH (vrh_quad.cpp); false = the scene keeps the binary
 // path (containment or box validity does not hold, or the root is a leaf)
+// `fz` (optional): the fused records of the AO kernel's 4-wide step (vrh_fused_slab.h) -- the same records over
+// boxes widened for ray origins within `omax` (and by at least `extra`), and per leaf-ordered primitive the
+// entry (record * 4 + entry) of `out` that holds its leaf's exact box.  Built only if every node's box is valid
+// and lies inside its parent's; `out` does not depend on it.
+struct fused_records
+{
+    float omax = 0.0f, extra = 0.0f;              // in
+    uint32_t num_indices = 0;                     // in: leaf-ordered primitives
+    std::vector<float> recs;                      // out
+    std::vector<uint32_t> leaf_slot;              // out
+    bool built = false;                           // out
+};
 bool build_quads(const node32* nodes, uint32_t num_nodes, std::vector<float>& out, uint32_t& root_link,
-                 uint32_t& quad_depth);
+                 uint32_t& quad_depth, fused_records* fz = nullptr);
 
 int build_bvh(const void* prims, uint32_t n, uint32_t kind, node32* nodes_out, uint32_t* num_nodes_out,
               uint32_t* indices_out, uint32_t* max_depth_out);

@@ -96,13 +96,22 @@ struct render_params
     unsigned long long* tile_times;
     uint32_t descent_cap;     // step loop: inner visits per step before a descent is resumed later
     uint32_t step_flags;      // step loop: bit 0 a descent that misses both children pops and continues;
-                              // bit 1 wave-uniform pair records fetched through the scalar cache
+                              // bit 1 wave-uniform pair records fetched through the scalar cache; bit 2 (AO
+                              // kernel) the 4-wide rays walk the fused records (aoquads, below)
     dev::shade_params shade;  // VRH_KERNEL_SIMPLE / MULTI_HIT: materials, lights, normal binding, ambient
     uint32_t max_hits;        // VRH_KERNEL_MULTI_HIT: N
     uint32_t num_bounces;     // VRH_KERNEL_WHITTED / PATHTRACING: loop iterations (eps = scene epsilon)
     uint32_t* mh_prim_id;     // [pixel][N] hit lists (render target side buffers)
     float* mh_t;
     dev::hit_mask_params hmask;   // mask intersector (vrh_hit_mask), hmask.mask == null: none
+    // the AO kernel's 4-wide records (appended: no other argument moves): `quads`, or with step_flags bit 2 the
+    // fused records over widened boxes (vrh_fused_slab.h) -- then a hit counts only if its leaf's exact box,
+    // entry leaf_slot[primitive] of `quads`, passes the exact test, and only rays with origins within fused_omax
+    // use them
+    const float4* aoquads;
+    const uint32_t* leaf_slot;
+    float fused_omax;
+    float ao_reach;           // (eps + radius) * 1.001f in float: the AO reach of the tile cut (ao_cut_build)
 };
 
 constexpr int COUNTERS_FRAME = 208;     // u64 words reset before every frame
@@ -110,7 +119,8 @@ constexpr int COUNTERS_LINES = 80;      // [80] L1 128-B lines, [81] wave-level 
                                         // [83] 4-lane-group accesses, [84] ideal-grouping accesses (counting variant)
 constexpr int COUNTERS_HANDOUT = 96;    // [96..99] wave time (wall_clock64 ticks summed over waves): AO hand-out, primary hand-out,
                                         // traversal step, whole loop; [100..102] AO hand-out events, rays, slot runs (counting
-                                        // variant of the AO step loop, test_counts::t_* / ho_*)
+                                        // variant of the AO step loop, test_counts::t_* / ho_*); [103] [104] hits checked
+                                        // against their leaf's exact box and checks that failed (fused records)
 constexpr int COUNTERS_TOTAL = 208;     // u64 words [208], [209]: totals
 constexpr int COUNTERS_WORDS = 256;
 constexpr int VRH_MAX_FRAME_LANES = 4;  // asynchronous frames: frame lanes of a context, at most

@@ -111,24 +111,41 @@ __device__ __forceinline__ bool tile_pixel(const render_params& P, uint32_t unit
 
 // per-wave totals (rays, hits, test counts): one atomic set per wave, at the end of the kernel
 // (AO: the AO step loop's time spans and hand-out counts as well)
-template <bool COUNT, bool AO>
+// FRESH: `lane` is lane_again()'s, and the two sums are shuffled by it -- __shfl_down would reuse the lane
+// number the kernel formed at its start, which then has to live, or be spilled, through the whole step loop
+__device__ __forceinline__ uint32_t lane_again()
+{
+    uint32_t z = 0u;
+    asm volatile("" : "+v"(z));                    // opaque: not merged with the kernel's first mbcnt
+    return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, z));
+}
+__device__ __forceinline__ unsigned long long down_by(unsigned long long v, uint32_t lane, int off)
+{
+    const int src = int((lane + uint32_t(off) < 64u ? lane + uint32_t(off) : lane) << 2);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)(uint32_t)v);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)(uint32_t)(v >> 32));
+    return ((unsigned long long)hi << 32) | lo;
+}
+template <bool COUNT, bool AO, bool FRESH = false>
 __device__ __forceinline__ void flush_totals(const render_params& P, uint32_t lane, uint64_t rays_total,
                                              uint64_t hits_total, const test_counts& cnt)
 {
     unsigned long long rr = rays_total, hh = hits_total, b = cnt.box, q = cnt.prim, uni_sum = cnt.w_uni;
     unsigned long long li = cnt.lines, rq = cnt.reqs, vm = cnt.vmem, a4 = cnt.acc4, ai = cnt.acc_ideal;
+    unsigned long long fc = cnt.fz_checks, fr = cnt.fz_rejects;
     unsigned long long ak[5];
     for (int k = 0; k < 5; ++k) ak[k] = cnt.acc_kind[k];
     for (int off = 32; off > 0; off >>= 1)
     {
-        rr += __shfl_down(rr, off);
-        hh += __shfl_down(hh, off);
+        if constexpr (FRESH) { rr += down_by(rr, lane, off); hh += down_by(hh, lane, off); }
+        else { rr += __shfl_down(rr, off); hh += __shfl_down(hh, off); }
         if (COUNT)
         {
             b += __shfl_down(b, off); q += __shfl_down(q, off); uni_sum += __shfl_down(uni_sum, off);
             li += __shfl_down(li, off); rq += __shfl_down(rq, off); vm += __shfl_down(vm, off);
             a4 += __shfl_down(a4, off); ai += __shfl_down(ai, off);
             for (int k = 0; k < 5; ++k) ak[k] += __shfl_down(ak[k], off);
+            fc += __shfl_down(fc, off); fr += __shfl_down(fr, off);
         }
     }
     if (__ballot(cnt.aborted) != 0ull && lane == 0) atomicOr(P.counters + 5, 1ull);
@@ -162,6 +179,8 @@ __device__ __forceinline__ void flush_totals(const render_params& P, uint32_t la
                 atomicAdd(P.counters + COUNTERS_HANDOUT + 4, (unsigned long long)cnt.ho_events);
                 atomicAdd(P.counters + COUNTERS_HANDOUT + 5, (unsigned long long)cnt.ho_rays);
                 atomicAdd(P.counters + COUNTERS_HANDOUT + 6, (unsigned long long)cnt.ho_runs);
+                atomicAdd(P.counters + COUNTERS_HANDOUT + 7, fc);
+                atomicAdd(P.counters + COUNTERS_HANDOUT + 8, fr);
             }
         }
     }
@@ -476,7 +495,8 @@ __device__ __forceinline__ uint32_t ao_cut_build(const render_params& P, const f
         hi[a] = ufl(wave_max(v ? x : -INFINITY));
         mag = fmaxf(mag, fmaxf(fabsf(lo[a]), fabsf(hi[a])));
     }
-    const float ext = ufl((P.eps + P.radius) * 1.001f + 1e-4f * (1.0f + mag));
+    // (the reach is the same for every tile: formed by the host, so that no VGPR holds it through the tile loop)
+    const float ext = ufl(P.ao_reach + 1e-4f * (1.0f + mag));
     if (!(ext < INFINITY)) return NONE;
     for (int a = 0; a < 3; ++a) { lo[a] -= ext; hi[a] += ext; }
     auto put = [&](float* e, cut_cfloat* q, uint32_t c) {           // entry c of record q -> e
@@ -495,8 +515,8 @@ __device__ __forceinline__ uint32_t ao_cut_build(const render_params& P, const f
     float* cur = cut;
     float* nxt = cut + 8u * CUT_MAX;
     {
-        const uint32_t ok = cut_children(P.quads, 0u, lo, hi);
-        cut_cfloat* q = (cut_cfloat*)(const float*)(P.quads);
+        const uint32_t ok = cut_children(P.aoquads, 0u, lo, hi);
+        cut_cfloat* q = (cut_cfloat*)(const float*)(P.aoquads);
         uint32_t n = 0;
         for (uint32_t c = 0; c < 4u; ++c)
             if (ok & (1u << c)) { put(cur + 8u * n, q, c); n += 1u; }
@@ -514,7 +534,7 @@ __device__ __forceinline__ uint32_t ao_cut_build(const render_params& P, const f
                 const uint32_t k = uu(__float_as_uint(cur[8u * j + 6u]));
                 if (k & LEAF_BIT) { total += 1u; continue; }
                 inner += 1u;
-                total += (uint32_t)__popc(cut_children(P.quads, k, lo, hi));
+                total += (uint32_t)__popc(cut_children(P.aoquads, k, lo, hi));
             }
             if (inner == 0u || total > CUT_MAX) break;
             uint32_t o = 0;
@@ -528,9 +548,9 @@ __device__ __forceinline__ uint32_t ao_cut_build(const render_params& P, const f
                     o += 1u;
                     continue;
                 }
-                const uint32_t ok = cut_children(P.quads, k, lo, hi);
+                const uint32_t ok = cut_children(P.aoquads, k, lo, hi);
                 if (COUNT && lane == 0u) cnt.box += 4u;
-                cut_cfloat* q = (cut_cfloat*)(const float*)(P.quads) + 32u * k;
+                cut_cfloat* q = (cut_cfloat*)(const float*)(P.aoquads) + 32u * k;
                 for (uint32_t c = 0; c < 4u; ++c)
                     if (ok & (1u << c)) { put(nxt + 8u * o, q, c); o += 1u; }
             }
@@ -983,6 +1003,11 @@ __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params 
             bk = 0; res_t = FMAX; res_prim = 0;
             const bool fin = finite_ray(r);
             quad = P.quad_ok && fin;
+            // the fused records serve rays that start within fused_omax (vrh_fused_slab.h ray_ok); any other ray
+            // walks the binary records
+            if constexpr (!LIST && (VRH_QUAD_STEP & 8) != 0)
+                if (P.step_flags & 4u)
+                    quad = quad && fused::ray_ok(r.ori.x, r.ori.y, r.ori.z, r.inv.x, r.inv.y, r.inv.z, P.fused_omax);
             st.reset(); resume = NO_RESUME;
             if (!LIST && (!SPILL || VRH_AO_CUT_SPILL) && VRH_AO_CUT && quad && cutn != NONE)
             {
@@ -1205,8 +1230,8 @@ __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params 
                 // of BVHs has no 4-wide records: its instances keep the plain call)
                 const float mt = VRH_AO_LEAN ? (any ? P.radius : FMAX) : max_t;
                 rc = (P.fast_ok && __ballot((tag & TAG_NONFINITE) != 0u) == 0ull)
-                    ? ray_step<KIND, COUNT, true, false, void, AO_CAPPED, !LIST>(P.pairs, P.prims, P.quads, 0u, quad, r, mt, any, st, best_t, best_prim, cnt, steps, P.step_limit, resume, P.descent_cap, P.step_flags, nullptr, static_cast<const void*>(nullptr), hm)
-                    : ray_step<KIND, COUNT, false, false, void, AO_CAPPED, !LIST>(P.pairs, P.prims, P.quads, 0u, quad, r, mt, any, st, best_t, best_prim, cnt, steps, P.step_limit, resume, P.descent_cap, P.step_flags, nullptr, static_cast<const void*>(nullptr), hm);
+                    ? ray_step<KIND, COUNT, true, false, void, AO_CAPPED, !LIST>(P.pairs, P.prims, LIST ? P.quads : P.aoquads, 0u, quad, r, mt, any, st, best_t, best_prim, cnt, steps, P.step_limit, resume, P.descent_cap, P.step_flags, nullptr, static_cast<const void*>(nullptr), hm, P.quads, P.leaf_slot)
+                    : ray_step<KIND, COUNT, false, false, void, AO_CAPPED, !LIST>(P.pairs, P.prims, LIST ? P.quads : P.aoquads, 0u, quad, r, mt, any, st, best_t, best_prim, cnt, steps, P.step_limit, resume, P.descent_cap, P.step_flags, nullptr, static_cast<const void*>(nullptr), hm, P.quads, P.leaf_slot);
             }
             if constexpr (LIST)
                 if (busy && rc < 0) rc = list_next(P, any, bk, res_t, res_prim, best_t, best_prim, st, resume);
@@ -1274,8 +1299,11 @@ __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params 
         if constexpr (COUNT) cnt.t_loop = wall_clock64() - cnt.t_loop;
     }
 
-    if (wt_slot && __lane_id() == 0u) wt_slot[1] = wall_clock64();
-    flush_totals<COUNT, AO>(P, __lane_id(), rays_total, hits_total, cnt);
+    // (the AO step loop's uncounted instances: a lane number formed anew, see flush_totals)
+    constexpr bool FRESH = AO && !COUNT && !LIST && (VRH_QUAD_STEP & 8) != 0;
+    const uint32_t lane_end = FRESH ? lane_again() : __lane_id();
+    if (wt_slot && lane_end == 0u) wt_slot[1] = wall_clock64();
+    flush_totals<COUNT, AO, FRESH>(P, lane_end, rays_total, hits_total, cnt);
 }
 
 // un-interleave gathered packed shards [count][rows_per_shard][W] into the full image (vrh_plan.h

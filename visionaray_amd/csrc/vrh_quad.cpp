@@ -18,8 +18,10 @@
 // link = quad index of an inner grandchild, LEAF_BIT | first primitive (leaf order) of a leaf,
 // QUAD_NONE for an unused entry.
 #include "vrh_internal.h"
+#include "../../include/visionaray_hip/detail/vrh_fused_slab.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <deque>
 #include <unordered_map>
@@ -46,14 +48,33 @@ bool inside(const node32& g, const node32& p)
     return true;
 }
 
+// every box valid and every child's box inside its parent's: then a leaf's own exact box test implies the test
+// of each of its ancestors, which is what lets a hit found through the fused records be verified against the
+// leaf's box alone (fused_records)
+bool nested(const node32* nodes, uint32_t num_nodes)
+{
+    for (uint32_t n = 0; n < num_nodes; ++n)
+    {
+        if (!valid_box(nodes[n])) return false;
+        if (nodes[n].num_prims != 0) continue;
+        const uint32_t fc = nodes[n].first;
+        if (uint64_t(fc) + 1 >= num_nodes) return false;
+        if (!inside(nodes[fc], nodes[n]) || !inside(nodes[fc + 1], nodes[n])) return false;
+    }
+    return true;
+}
+
 } // namespace
 
 bool build_quads(const node32* nodes, uint32_t num_nodes, std::vector<float>& out, uint32_t& root_link,
-                 uint32_t& quad_depth)
+                 uint32_t& quad_depth, fused_records* fz)
 {
     out.clear();
     quad_depth = 0;
+    if (fz) { fz->recs.clear(); fz->leaf_slot.clear(); fz->built = false; }
     if (num_nodes < 3 || nodes[0].num_prims != 0) return false;     // single leaf: nothing to widen
+    bool fuse = fz != nullptr && nested(nodes, num_nodes) && fz->omax <= 0x1p100f;
+    if (fuse) fz->leaf_slot.assign(fz->num_indices, QUAD_NONE);
     std::unordered_map<uint32_t, uint32_t> index;                    // binary inner node -> quad
     std::deque<std::pair<uint32_t, uint32_t>> queue;                 // (binary node, quad depth)
     index[0] = 0;
@@ -129,9 +150,44 @@ bool build_quads(const node32* nodes, uint32_t num_nodes, std::vector<float>& ou
             }
             const uint32_t l = used ? links[e] : QUAD_NONE;
             std::memcpy(&rec[24 + e], &l, 4);
+            if (fuse && used && (l & 0x80000000u))
+            {
+                // the leaf's exact box is entry e of this record: every primitive of the leaf names it
+                const uint64_t first = l & 0x7FFFFFFFu, count = b.num_prims;
+                if (first + count > fz->num_indices) { fuse = false; continue; }
+                for (uint64_t i = first; i < first + count; ++i) fz->leaf_slot[i] = q * 4u + e;
+            }
         }
     }
     root_link = 0;
+    if (fuse)
+    {
+        // the same records and links over boxes widened outward (vrh_fused_slab.h); an unused entry is a point
+        // box at +inf, which no finite ray passes
+        fz->recs = out;
+        for (size_t q = 0; q < out.size() / 32 && fuse; ++q)
+        {
+            float* rec = &fz->recs[q * 32];
+            for (uint32_t e = 0; e < 4; ++e)
+            {
+                uint32_t l;
+                std::memcpy(&l, &rec[24 + e], 4);
+                for (int a = 0; a < 3; ++a)
+                {
+                    float& lo = rec[a * 4 + e];
+                    float& hi = rec[12 + a * 4 + e];
+                    lo = l == QUAD_NONE ? INFINITY : fused::widen_lo(lo, fz->omax, fz->extra);
+                    hi = l == QUAD_NONE ? INFINITY : fused::widen_hi(hi, fz->omax, fz->extra);
+                    if (l != QUAD_NONE && !(std::isfinite(lo) && std::isfinite(hi))) fuse = false;
+                }
+            }
+        }
+    }
+    if (fz)
+    {
+        fz->built = fuse;
+        if (!fuse) { fz->recs.clear(); fz->leaf_slot.clear(); }
+    }
     return true;
 }
 

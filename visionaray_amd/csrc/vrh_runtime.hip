@@ -187,6 +187,8 @@ constexpr option_range k_option_ranges[] = {
     { VRH_OPT_CLUSTER_TILES, 0, 1024, "cluster tiles is 0 (auto) or 1..1024" },
     { VRH_OPT_QUAD_REFILL, 0, 1, "the quad-coherent hand-out was removed (0 is accepted)" },
     { VRH_OPT_GROUP_UNITS, 0, 1, "the block-shared hand-out was removed (0 is accepted)" },
+    { VRH_OPT_FUSED_STEP, 0, 2, "fused step is 0 (auto), 1 (on) or 2 (off)" },
+    { VRH_OPT_FUSED_WIDEN, 0, 30, "fused widening is 0 (the derived widening) or 1..30 (at least the scene extent x 2^-value)" },
     { VRH_OPT_ASYNC_FRAMES, 0, VRH_MAX_FRAME_LANES, "asynchronous frames is 0 (off), 1 (on, the default number of frame lanes) or 2..4 (on, that many frame lanes)" },
 };
 
@@ -228,6 +230,8 @@ VRH_API int vrh_ctx_set_option(vrh_ctx* ctx, uint32_t option, int64_t value)
     case VRH_OPT_AO_GATE: ctx->opt.gate = v; break;
     case VRH_OPT_POP_ON_MISS: ctx->opt.pop = v; break;
     case VRH_OPT_PAIR_LAYOUT: ctx->opt.layout = v; break;
+    case VRH_OPT_FUSED_WIDEN: ctx->opt_fused_widen = v; break;
+    case VRH_OPT_FUSED_STEP: ctx->opt_fused_step = v; break;
     case VRH_OPT_SCALAR_FETCH: ctx->opt.scalar = v; break;
     case VRH_OPT_REFILL_MIN: ctx->opt.refill = v; break;
     case VRH_OPT_BLOCKS_PER_CU: ctx->opt.bpc = v; break;
@@ -413,7 +417,24 @@ VRH_API int vrh_scene_upload(vrh_ctx* ctx, const void* nodes_v, uint32_t num_nod
 
     std::vector<float> quads;
     uint32_t quad_root = 0, quad_depth = 0;
-    const bool have_quads = finite_bounds && build_quads(nodes, num_nodes, quads, quad_root, quad_depth);
+    // the fused records (vrh_fused_slab.h) serve ray origins within twice the root box's largest coordinate: an
+    // AO ray starts on a surface, inside the root box; a ray from farther out walks the binary records
+    // (only in a build whose kernels walk them, VRH_QUAD_STEP & 8 -- libvrh_fused.so; VRH_OPT_FUSED_STEP 2 leaves them out)
+    fused_records fz;
+    const bool want_fused = (VRH_QUAD_STEP & 8) != 0 && ctx->opt_fused_step != 2;
+    if (finite_bounds)
+    {
+        float extent = 0.0f;
+        for (int a = 0; a < 3; ++a)
+        {
+            fz.omax = std::max(fz.omax, 2.0f * std::max(std::fabs(nodes[0].bmin[a]), std::fabs(nodes[0].bmax[a])));
+            extent = std::max(extent, nodes[0].bmax[a] - nodes[0].bmin[a]);
+        }
+        fz.omax = vrh::fused::omax_floor(fz.omax);
+        fz.extra = ctx->opt_fused_widen ? std::ldexp(extent, -ctx->opt_fused_widen) : 0.0f;
+        fz.num_indices = num_indices;
+    }
+    const bool have_quads = finite_bounds && build_quads(nodes, num_nodes, quads, quad_root, quad_depth, want_fused ? &fz : nullptr);
 
     int rc = select_device(ctx);
     if (rc) return rc;
@@ -443,6 +464,31 @@ VRH_API int vrh_scene_upload(vrh_ctx* ctx, const void* nodes_v, uint32_t num_nod
         sc->info.wide_records = uint32_t(quads.size() / 32);
         sc->info.wide_depth = quad_depth;
         bytes += qb;
+        if (fz.built)
+        {
+            // VRH_QUAD_STEP & 32: instead of the slots, the exact boxes themselves, two float4 per leaf-ordered primitive
+            std::vector<float> boxes;
+            if (VRH_QUAD_STEP & 32)
+            {
+                boxes.assign(size_t(8) * fz.leaf_slot.size(), 0.0f);
+                for (size_t i = 0; i < fz.leaf_slot.size(); ++i)
+                {
+                    const uint32_t s = fz.leaf_slot[i];
+                    if (s == QUAD_NONE) continue;
+                    const float* rec = &quads[size_t(s >> 2) * 32 + (s & 3u)];
+                    for (int a = 0; a < 3; ++a) { boxes[8 * i + a] = rec[4 * a]; boxes[8 * i + 4 + a] = rec[12 + 4 * a]; }
+                }
+            }
+            const void* aux = (VRH_QUAD_STEP & 32) ? static_cast<const void*>(boxes.data()) : static_cast<const void*>(fz.leaf_slot.data());
+            const size_t sb = (VRH_QUAD_STEP & 32) ? boxes.size() * sizeof(float) : fz.leaf_slot.size() * sizeof(uint32_t);
+            if ((e = hipMalloc(&sc->fquads, qb)) != hipSuccess) return fail(e, "hipMalloc(fused records)");
+            if ((e = hipMemcpy(sc->fquads, fz.recs.data(), qb, hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "upload fused records");
+            if ((e = hipMalloc(&sc->leaf_slot, sb)) != hipSuccess) return fail(e, "hipMalloc(leaf slots)");
+            if ((e = hipMemcpy(sc->leaf_slot, aux, sb, hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "upload leaf slots");
+            sc->fused_omax = fz.omax;
+            sc->info.fused_records = sc->info.wide_records;
+            sc->info.fused_bytes = qb + sb;       // not part of device_bytes, which the launch plan reads
+        }
     }
     if (face_normals)
     {
@@ -500,6 +546,8 @@ VRH_API int vrh_scene_free(vrh_scene* sc)
     if (sc->prims) (void)hipFree(sc->prims);
     if (sc->normals) (void)hipFree(sc->normals);
     if (sc->quads) (void)hipFree(sc->quads);
+    if (sc->fquads) (void)hipFree(sc->fquads);
+    if (sc->leaf_slot) (void)hipFree(sc->leaf_slot);
     if (sc->vnormals) (void)hipFree(sc->vnormals);
     if (sc->dnodes) (void)hipFree(sc->dnodes);
     if (sc->dindices) (void)hipFree(sc->dindices);
@@ -1365,6 +1413,15 @@ int fill_params(render_params& p, const launch_plan& plan, const vrh_ctx* ctx, c
     p.stack_cap = uint32_t(plan.cfg.stack_cap); p.stack_total = plan.stack_total; p.quad_lds = plan.quad_lds;
     p.fast_ok = plan.fast_ok;
     p.quads = sc->quads; p.quad_ok = plan.quad_ok;
+    // the AO kernel's 4-wide rays walk the fused records where the scene has them (VRH_QUAD_STEP & 8): step_flags
+    // bit 2, and the exact records stay at hand for the verification of a hit
+    p.aoquads = sc->quads; p.leaf_slot = nullptr; p.fused_omax = 0.0f;
+    p.ao_reach = (k->eps + k->radius) * 1.001f;
+    if ((VRH_QUAD_STEP & 8) && ao && plan.quad_ok && sc->fquads && sc->num_roots == 1)
+    {
+        p.aoquads = sc->fquads; p.leaf_slot = sc->leaf_slot; p.fused_omax = sc->fused_omax;
+        p.step_flags |= 4u;
+    }
     p.ao_cut = plan.ao_cut; p.ao_share = plan.ao_share;
     for (uint32_t f = 0; f < num_frames; ++f)
     {
@@ -1763,7 +1820,7 @@ VRH_API int vrh_last_handout_stats(vrh_ctx* ctx, vrh_handout_stats* stats)
     int rc = select_device(ctx);
     if (rc) return rc;
     VRH_HIP(hipEventSynchronize(ctx->ev_stop[ctx->last_slot]));
-    unsigned long long c[7];
+    unsigned long long c[9];
     VRH_HIP(hipMemcpy(c, ctx->last_counters + COUNTERS_HANDOUT, sizeof(c), hipMemcpyDeviceToHost));
     vrh_handout_stats s{};
     s.ao_handout_ticks = c[0];
@@ -1773,6 +1830,8 @@ VRH_API int vrh_last_handout_stats(vrh_ctx* ctx, vrh_handout_stats* stats)
     s.ao_handout_events = c[4];
     s.ao_handout_rays = c[5];
     s.ao_handout_slot_runs = c[6];
+    s.fused_checks = c[7];
+    s.fused_rejects = c[8];
     *stats = s;
     return VRH_OK;
 }
