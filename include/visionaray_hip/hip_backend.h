@@ -27,10 +27,12 @@
 #include "../vrh.h"
 
 #include <atomic>
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
 #include <iterator>
+#include <limits>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -195,6 +197,13 @@ public:
     {
         vrh_frame_stats s{};
         hip_detail::check(vrh_last_frame_stats(get(), &s), "vrh_last_frame_stats");
+        return s;
+    }
+    // rays, steps and the capped flag of the last volume frame (waits for it)
+    vrh_volume_stats volume_last_stats() const
+    {
+        vrh_volume_stats s{};
+        hip_detail::check(vrh_volume_last_stats(get(), &s), "vrh_volume_last_stats");
         return s;
     }
 
@@ -841,6 +850,86 @@ private:
     std::shared_ptr<vrh_hit_mask> mask_;
 };
 
+//-------------------------------------------------------------------------------------------------
+// Volume rendering (vrh.h vrh_render_volume): the kernel of src/examples/volume/main.cpp:123-167 --
+// tex3D of a scalar volume, tex1D of an RGBA transfer function, front-to-back compositing in a box.
+//
+
+// hip_volume: the volume's voxels (texture_ref<float | unorm<8> | unorm<16>, 3>: float, uint8_t or uint16_t
+// data, x fastest) and its transfer function (texture_ref<vec4, 1>: `tf_size` RGBA float entries) on the
+// device.  filter: 0 nearest, 1 linear; address: 0 wrap, 1 mirror, 2 clamp (the reference's enum values).
+class hip_volume
+{
+public:
+    template <typename T>
+    hip_volume(T const* voxels, size_t w, size_t h, size_t d, int filter, int address, float const* tf_rgba, size_t tf_size,
+               int tf_filter, int tf_address, std::shared_ptr<hip_context> ctx = hip_context::default_context())
+        : ctx_(std::move(ctx))
+    {
+        static_assert(std::is_same<T, float>::value || sizeof(T) == 1 || sizeof(T) == 2,
+                      "hip_volume: float, 8-bit (unorm<8>) or 16-bit (unorm<16>) voxels");
+        vrh_volume_desc vd{};
+        vd.voxels = voxels;
+        vd.width = uint32_t(w); vd.height = uint32_t(h); vd.depth = uint32_t(d);
+        vd.format = std::is_same<T, float>::value ? VRH_VOL_R32F : sizeof(T) == 1 ? VRH_VOL_R8 : VRH_VOL_R16;
+        vd.filter = uint32_t(filter);
+        vd.address[0] = vd.address[1] = vd.address[2] = uint32_t(address);
+        const vrh_transfunc_desc td{ tf_rgba, uint32_t(tf_size), uint32_t(tf_filter), uint32_t(tf_address) };
+        vrh_volume* v = nullptr;
+        hip_detail::check(vrh_volume_create(ctx_->get(), &vd, &td, &v), "vrh_volume_create");
+        vol_.reset(v, [](vrh_volume* p) { vrh_volume_free(p); });
+    }
+
+    // replaces the transfer function between two frames
+    void set_transfunc(float const* tf_rgba, size_t tf_size, int tf_filter, int tf_address)
+    {
+        const vrh_transfunc_desc td{ tf_rgba, uint32_t(tf_size), uint32_t(tf_filter), uint32_t(tf_address) };
+        hip_detail::check(vrh_volume_set_transfunc(vol_.get(), &td), "vrh_volume_set_transfunc");
+    }
+
+    vrh_volume* handle() const { return vol_.get(); }
+    hip_context& context() const { return *ctx_; }
+
+private:
+    std::shared_ptr<hip_context> ctx_;
+    std::shared_ptr<vrh_volume> vol_;
+};
+
+// what hip_sched::frame takes for a volume frame
+struct volume_kernel
+{
+    vrh_volume* volume;
+    vrh_volume_kernel_desc desc;
+};
+
+// The example's kernel over `volume` in `bbox` (any type with .min / .max of .x .y .z): axis d of the box
+// maps onto [0, 1] of the texture, reversed where flipped -- the defaults are the example's
+// ((pos.x + 1) / 2, (-pos.y + 1) / 2, (-pos.z + 1) / 2 for the box [-1, 1]^3, dt 0.01, cutoff 0.999).
+// The cutoff is a double as in the example; the kernel gets the smallest float that is not below it.
+template <typename AABB>
+volume_kernel make_hip_volume_kernel(hip_volume const& volume, AABB const& bbox, float dt = 0.01f, double opacity_cutoff = 0.999,
+                                     bool flip_x = false, bool flip_y = true, bool flip_z = true)
+{
+    volume_kernel k{};
+    k.volume = volume.handle();
+    const float lo[3] = { float(bbox.min.x), float(bbox.min.y), float(bbox.min.z) };
+    const float hi[3] = { float(bbox.max.x), float(bbox.max.y), float(bbox.max.z) };
+    const bool flip[3] = { flip_x, flip_y, flip_z };
+    for (int a = 0; a < 3; ++a)
+    {
+        k.desc.box_min[a] = lo[a];
+        k.desc.box_max[a] = hi[a];
+        k.desc.coord_sign[a] = flip[a] ? -1.0f : 1.0f;
+        k.desc.coord_offset[a] = flip[a] ? hi[a] : -lo[a];
+        k.desc.coord_extent[a] = hi[a] - lo[a];
+    }
+    k.desc.dt = dt;
+    float c = float(opacity_cutoff);
+    if (double(c) < opacity_cutoff) c = std::nextafter(c, std::numeric_limits<float>::infinity());
+    k.desc.opacity_cutoff = c;
+    return k;
+}
+
 // closest_hit(ray, begin, end, intersector) / any_hit(..., intersector) for every ray of a built-in
 // kernel (traverse_linear.inl:232-329): the kernel with the mask intersector attached
 inline hip_builtin_kernel with_intersector(hip_builtin_kernel k, hip_hit_mask const& mask)
@@ -989,7 +1078,12 @@ public:
     template <typename K, typename SP>
     void frame(K kernel, SP sparams, unsigned frame_num = 0, vrh_shard const* shard = nullptr)
     {
-        if constexpr (!std::is_same<K, hip_builtin_kernel>::value)
+        if constexpr (std::is_same<K, volume_kernel>::value)
+        {
+            if (shard) throw std::runtime_error("hip_sched::frame: the volume kernel renders no shards");
+            frame_volume(kernel, sparams);
+        }
+        else if constexpr (!std::is_same<K, hip_builtin_kernel>::value)
         {
             static_assert(hip_detail::user_kernels<K>::available,
                           "hip_sched runs the built-in kernels (make_hip_closest_hit_kernel / make_hip_ao_kernel / "
@@ -1005,6 +1099,27 @@ public:
     }
 
 private:
+    // the volume kernel (vrh_render_volume): the uniform sampler and a pinhole camera, whole image or scissor box
+    template <typename SP>
+    void frame_volume(volume_kernel const& kernel, SP& sparams)
+    {
+        static_assert(hip_detail::uniform_sampler<SP>(), "hip_sched::frame: the volume kernel takes pixel_sampler::uniform_type");
+        static_assert(!hip_detail::has_camera_matrices<SP>::value, "hip_sched::frame: the volume kernel takes a camera, not matrices");
+        if (group_) throw std::runtime_error("hip_sched::frame: the volume kernel renders on one GPU (no render groups)");
+        auto const& cam = sparams.cam;
+        auto& rt = sparams.rt;
+        float eye[3] = { cam.eye().x, cam.eye().y, cam.eye().z };
+        float center[3] = { cam.center().x, cam.center().y, cam.center().z };
+        float up[3] = { cam.up().x, cam.up().y, cam.up().z };
+        vrh_camera c{};
+        hip_detail::check(vrh_make_camera(eye, center, up, cam.fovy(), cam.aspect(), uint32_t(rt.width()),
+                                          uint32_t(rt.height()), &c), "vrh_make_camera");
+        hip_detail::set_scissor(sparams, c);
+        rt.begin_frame();
+        hip_detail::check(vrh_render_volume(ctx_->get(), kernel.volume, rt.handle(), &c, &kernel.desc), "vrh_render_volume");
+        rt.end_frame();
+    }
+
     template <typename SP>
     void frame_builtin(hip_builtin_kernel const& kernel, SP& sparams, unsigned frame_num, vrh_shard const* shard)
     {

@@ -58,6 +58,7 @@
 #include "detail/vrh_device.h"
 #include "detail/vrh_libm.h"
 #include "detail/vrh_sampler.h"
+#include "detail/vrh_volume.h"
 
 #include <array>
 #include <atomic>
@@ -201,6 +202,27 @@ public:
     T depth;
     vector<3, T> isect_pos;
 };
+
+// ray / box (math/intersect.h:28-81): the clip of the volume example, with the reference's scalar min / max
+template <typename T>
+struct hit_record<basic_ray<T>, aabb>
+{
+    using scalar_type = T;
+    using mask_type = bool;
+    VRH_FUNC hit_record() : hit(false), tnear(FLT_MAX), tfar(-FLT_MAX) {}
+    bool hit;
+    T tnear;
+    T tfar;
+};
+
+VRH_FUNC inline hit_record<basic_ray<float>, aabb> intersect(basic_ray<float> const& ray, aabb const& box)
+{
+    hit_record<basic_ray<float>, aabb> hr;
+    const float o[3] = { ray.ori.x, ray.ori.y, ray.ori.z }, d[3] = { ray.dir.x, ray.dir.y, ray.dir.z };
+    const float lo[3] = { box.min.x, box.min.y, box.min.z }, hi[3] = { box.max.x, box.max.y, box.max.z };
+    hr.hit = vrh::dev::box_clip(o, d, lo, hi, hr.tnear, hr.tfar);
+    return hr;
+}
 
 // width-1 unpack (vector*.inl unpack, hit_record.h:103-130): the one lane
 template <typename T>
@@ -2524,6 +2546,46 @@ private:
     }
 };
 } // hip_detail
+
+//-------------------------------------------------------------------------------------------------
+// Volume textures in user kernels: device refs over a hip_volume's views (vrh_volume_get_view) and the
+// reference's tex3D / tex1D on them -- the samplers of the built-in volume kernel
+// (visionaray_hip/detail/vrh_volume.h), so the volume example's lambda compiles as a user kernel and
+// renders the built-in's bits.  A ref is valid until the volume is destroyed (the transfer function's:
+// until the next set_transfunc).
+//
+
+struct hip_volume_ref { vrh::dev::vol_view view; };          // texture_ref<float | unorm<8> | unorm<16>, 3>
+struct hip_transfunc_ref { vrh::dev::tf_view view; };        // texture_ref<vec4, 1>
+
+inline hip_volume_ref volume_ref(hip_volume const& v)
+{
+    vrh_volume_view vv{};
+    hip_detail::check(vrh_volume_get_view(v.handle(), &vv), "vrh_volume_get_view");
+    hip_volume_ref r{};
+    std::memcpy(&r.view, vv.volume, sizeof(r.view));
+    return r;
+}
+
+inline hip_transfunc_ref transfunc_ref(hip_volume const& v)
+{
+    vrh_volume_view vv{};
+    hip_detail::check(vrh_volume_get_view(v.handle(), &vv), "vrh_volume_get_view");
+    hip_transfunc_ref r{};
+    std::memcpy(&r.view, vv.transfunc, sizeof(r.view));
+    return r;
+}
+
+__device__ inline float tex3D(hip_volume_ref const& tex, vector<3, float> const& coord)
+{
+    return vrh::dev::tex3d(tex.view, coord.x, coord.y, coord.z);
+}
+
+__device__ inline vector<4, float> tex1D(hip_transfunc_ref const& tex, float coord)
+{
+    const vrh::dev::rgba_t c = vrh::dev::tex1d(tex.view, tex.view.entries, coord);
+    return vector<4, float>(c.x, c.y, c.z, c.w);
+}
 
 // the user traversal stack holds at most VRH_USER_STACK entries, and a BVH of depth d needs d + 1:
 // checked_ref rejects a deeper BVH on the host, and registers the depth of one it accepts, so that the

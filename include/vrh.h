@@ -506,6 +506,92 @@ typedef struct {
 VRH_API int vrh_pnm_load(const char* filename, vrh_pnm_image* out);
 VRH_API int vrh_pnm_free(vrh_pnm_image* image);
 
+/* ---- volume rendering <- src/examples/volume/main.cpp:123-167 -------------------------------------------
+ * The example's kernel: the primary ray is clipped against a box (intersect(ray, aabb),
+ * math/intersect.h:54-81) and marched from tnear in steps of dt while t < tfar.  Every step samples a scalar
+ * 3-D texture (tex3D, texture_ref<float | unorm<8> | unorm<16>, 3>), classifies the sample through an RGBA
+ * transfer function (tex1D, texture_ref<vec4, 1>, the voxel value is the coordinate), premultiplies
+ * (c.xyz *= c.w) and composites front to back (color += c * (1 - color.w)); the march ends early once
+ * color.w >= opacity_cutoff.  Restated bit for bit in visionaray_hip/detail/vrh_volume.h, one text for the
+ * kernel and for the host entry points below.  As in the reference a miss leaves colour (0, 0, 0, 0) (there
+ * is no background colour), tnear may be negative (the eye inside the box: the march starts behind the eye)
+ * and a box wholly behind the eye is marched.
+ * The texture coordinate of a position is tc[d] = (coord_sign[d] * pos[d] + coord_offset[d]) / coord_extent[d]
+ * with coord_sign +1 or -1: sign (1, -1, -1), offset 1, extent 2 are the example's coordinates for the box
+ * [-1, 1]^3.  The example compares the opacity with the double 0.999; opacity_cutoff is a float: pass the
+ * smallest float that is not below the double (for a float w, w >= c holds exactly when w >= that float). */
+typedef struct vrh_volume vrh_volume;   /* device-resident voxels + transfer function */
+enum vrh_volume_format { VRH_VOL_R8 = 0, VRH_VOL_R16 = 1, VRH_VOL_R32F = 2 };
+#define VRH_VOLUME_MAX_STEPS 65536u
+typedef struct {
+    const void* voxels;       /* width x height x depth voxels of `format`, x fastest, no padding */
+    uint32_t width, height, depth;
+    uint32_t format;          /* vrh_volume_format                                             */
+    uint32_t filter;          /* vrh_texture_filter                                            */
+    uint32_t address[3];      /* vrh_texture_address of x, y and z                             */
+} vrh_volume_desc;
+typedef struct {
+    const float* rgba;        /* size RGBA32F entries                                          */
+    uint32_t size;
+    uint32_t filter;          /* vrh_texture_filter                                            */
+    uint32_t address;         /* vrh_texture_address                                           */
+} vrh_transfunc_desc;
+typedef struct {
+    float box_min[3], box_max[3];
+    float coord_sign[3], coord_offset[3], coord_extent[3];
+    float dt;                 /* step along the (normalised) ray direction                     */
+    float opacity_cutoff;     /* early ray termination: color.w >= opacity_cutoff             */
+} vrh_volume_kernel_desc;
+typedef struct {
+    uint64_t rays;            /* pixels rendered                                               */
+    uint64_t steps;           /* samples taken over all rays                                   */
+    uint32_t capped;          /* a ray was stopped by the device's step limit                  */
+    uint32_t reserved;
+} vrh_volume_stats;
+/* Copies the voxels and the transfer function to the device.  VRH_ERR_INVALID: an unknown enum value, a
+ * dimension of 0 or above VRH_TEX_MAX_DIM (the transfer function's size included), more than
+ * VRH_TEX_MAX_TEXELS voxels, an R32F voxel or a transfer-function entry that is not finite, an R32F voxel
+ * above VRH_TEX_MAX_COORD in magnitude (the voxel is the transfer function's texture coordinate).  The
+ * descriptors are checked before the context is looked at. */
+VRH_API int vrh_volume_create(vrh_ctx* ctx, const vrh_volume_desc* volume, const vrh_transfunc_desc* transfunc,
+                              vrh_volume** out);
+/* replaces the transfer function (between frames: waits for the context's work first) */
+VRH_API int vrh_volume_set_transfunc(vrh_volume* volume, const vrh_transfunc_desc* transfunc);
+VRH_API int vrh_volume_free(vrh_volume* volume);
+/* The device views of a volume and of its current transfer function for user kernels compiled with hipcc
+ * (visionaray_hip/hip_kernels.h tex3D / tex1D): the bytes of visionaray_hip/detail/vrh_volume.h vol_view and
+ * tf_view, valid until vrh_volume_free / the next vrh_volume_set_transfunc. */
+typedef struct { uint64_t volume[10]; uint64_t transfunc[4]; } vrh_volume_view;
+VRH_API int vrh_volume_get_view(const vrh_volume* volume, vrh_volume_view* out);
+/* One frame of the volume kernel (visionaray_amd/csrc/vrh_volume.hip), asynchronous on the context stream
+ * and ordered with the context's other work like every entry point there.  The uniform pixel sampler and
+ * a pinhole camera (its scissor box honoured) only: no shards, no render groups, no frames in flight.
+ * VRH_RT_COLOR is written at every rendered pixel; VRH_RT_PRIM_ID, if the target has it, is 0 on a box hit
+ * and 0xFFFFFFFF on a miss; VRH_RT_T, if present, tnear on a hit and -1 on a miss; VRH_RT_OCC is untouched.
+ * Hang guard: VRH_ERR_INVALID if dt is not finite, dt <= 0, dt < D * 2^-20 with D the distance from the
+ * eye to the farthest box corner (above that t + dt > t always holds), or diagonal / dt >
+ * VRH_VOLUME_MAX_STEPS; on the device a ray stops after 2 * ceil(diagonal / dt) + 8 steps and raises a
+ * flag, which the next vrh_sync / vrh_rt_download / vrh_volume_last_stats reports as VRH_ERR_INVALID
+ * (once: the flag is then cleared). */
+VRH_API int vrh_render_volume(vrh_ctx* ctx, const vrh_volume* volume, vrh_rt* rt, const vrh_camera* cam,
+                              const vrh_volume_kernel_desc* kernel);
+VRH_API int vrh_volume_last_stats(vrh_ctx* ctx, vrh_volume_stats* stats);   /* of the last volume frame; syncs */
+/* the host build of the shared samplers: out[i] = tex3D(volume, coords[3 i ..]) and
+ * rgba_out[4 i ..] = tex1D(transfunc, coords[i]); the descriptor checks of vrh_volume_create, and every
+ * coordinate finite and at most VRH_TEX_MAX_COORD in magnitude */
+VRH_API int vrh_tex3d_host(const vrh_volume_desc* volume, const float* coords, uint32_t n, float* out);
+VRH_API int vrh_tex1d_host(const vrh_transfunc_desc* transfunc, const float* coords, uint32_t n, float* rgba_out);
+/* the host build of the whole frame: the checks and outputs of vrh_render_volume into host arrays of
+ * cam->width x cam->height pixels (any may be NULL; pixels outside the scissor box are left untouched);
+ * steps_px gets the samples taken per pixel */
+VRH_API int vrh_volume_render_host(const vrh_volume_desc* volume, const vrh_transfunc_desc* transfunc,
+                                   const vrh_camera* cam, const vrh_volume_kernel_desc* kernel, float* color,
+                                   uint32_t* prim_id, float* t, uint32_t* steps_px, vrh_volume_stats* stats);
+/* the samplers on the device: voxel_out[i] = tex3D(volume, coords[3 i ..]) and rgba_out[4 i ..] =
+ * tex1D(transfunc, voxel_out[i]) (either output may be NULL); synchronous */
+VRH_API int vrh_volume_sample(vrh_ctx* ctx, const vrh_volume* volume, const float* coords, uint32_t n,
+                              float* voxel_out, float* rgba_out);
+
 /* render targets.  vrh_rt_alloc owns its buffers (flags = vrh_rt_flags); vrh_rt_wrap borrows
  * caller device pointers (any may be NULL), e.g. torch tensors used for the RCCL gather. */
 VRH_API int vrh_rt_alloc(vrh_ctx* ctx, uint32_t width, uint32_t height, uint32_t flags, vrh_rt** out);

@@ -15,7 +15,8 @@ from .api import (BVH_NODE_DTYPE, DEGREES_TO_RADIANS, GROUP_ID_BYTES, MATERIAL_D
                   multi_hit_kernel, normals_per_face_binding, normals_per_vertex_binding, pathtracing_kernel, pixel_sampler,
                   plastic,
                   point_light, render, render_batch, render_group, render_sampled, render_sharded, render_view, sah_cost, shading,
-                  shard_bands, simple_kernel, tex_address, tex_filter, texture, unshard, view_camera, whitted_kernel, with_hit_mask)
+                  shard_bands, simple_kernel, tex3d_host, tex_address, tex_filter, texture, transfunc, unshard, view_camera, volume,
+                  volume_desc, volume_kernel, volume_kernel_desc, volume_render_host, whitted_kernel, with_hit_mask)
 
 __all__ = [
     "BVH_NODE_DTYPE", "DEGREES_TO_RADIANS", "GROUP_ID_BYTES", "MATERIAL_DTYPE", "MATERIAL_EMISSIVE", "MATERIAL_MATTE",
@@ -26,5 +27,6 @@ __all__ = [
     "multi_hit_kernel", "normals_per_face_binding", "normals_per_vertex_binding", "pathtracing_kernel", "pixel_sampler",
     "plastic",
     "point_light", "render", "render_batch", "render_group", "render_sampled", "render_sharded", "render_view", "sah_cost",
-    "shading", "shard_bands", "simple_kernel", "tex_address", "tex_filter", "texture", "unshard", "view_camera", "whitted_kernel", "with_hit_mask",
+    "shading", "shard_bands", "simple_kernel", "tex3d_host", "tex_address", "tex_filter", "texture", "transfunc", "unshard", "view_camera",
+    "volume", "volume_desc", "volume_kernel", "volume_kernel_desc", "volume_render_host", "whitted_kernel", "with_hit_mask",
 ]

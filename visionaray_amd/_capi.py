@@ -172,6 +172,33 @@ class vrh_pnm_image(C.Structure):
                 ("max_value", C.c_uint32)]
 
 
+VRH_VOL_R8, VRH_VOL_R16, VRH_VOL_R32F = 0, 1, 2
+VRH_VOLUME_MAX_STEPS = 65536
+
+
+class vrh_volume_desc(C.Structure):
+    _fields_ = [("voxels", C.c_void_p), ("width", C.c_uint32), ("height", C.c_uint32), ("depth", C.c_uint32),
+                ("format", C.c_uint32), ("filter", C.c_uint32), ("address", C.c_uint32 * 3)]
+
+
+class vrh_transfunc_desc(C.Structure):
+    _fields_ = [("rgba", C.c_void_p), ("size", C.c_uint32), ("filter", C.c_uint32), ("address", C.c_uint32)]
+
+
+class vrh_volume_kernel_desc(C.Structure):
+    _fields_ = [("box_min", C.c_float * 3), ("box_max", C.c_float * 3), ("coord_sign", C.c_float * 3),
+                ("coord_offset", C.c_float * 3), ("coord_extent", C.c_float * 3), ("dt", C.c_float),
+                ("opacity_cutoff", C.c_float)]
+
+
+class vrh_volume_view(C.Structure):
+    _fields_ = [("volume", C.c_uint64 * 10), ("transfunc", C.c_uint64 * 4)]
+
+
+class vrh_volume_stats(C.Structure):
+    _fields_ = [("rays", C.c_uint64), ("steps", C.c_uint64), ("capped", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class VrhError(RuntimeError):
     def __init__(self, fn, code, msg):
         super().__init__(f"{fn} failed (status {code}): {msg}")
@@ -269,6 +296,18 @@ SIGNATURES = {
     "vrh_tex2d_host": (C.c_int, [_vp, _vp, _u32, _vp]),
     "vrh_pnm_load": (C.c_int, [C.c_char_p, _vp]),
     "vrh_pnm_free": (C.c_int, [_vp]),
+    "vrh_volume_create": (C.c_int, [_vp, C.POINTER(vrh_volume_desc), C.POINTER(vrh_transfunc_desc), C.POINTER(_vp)]),
+    "vrh_volume_set_transfunc": (C.c_int, [_vp, C.POINTER(vrh_transfunc_desc)]),
+    "vrh_volume_free": (C.c_int, [_vp]),
+    "vrh_volume_get_view": (C.c_int, [_vp, C.POINTER(vrh_volume_view)]),
+    "vrh_render_volume": (C.c_int, [_vp, _vp, _vp, C.POINTER(vrh_camera), C.POINTER(vrh_volume_kernel_desc)]),
+    "vrh_volume_last_stats": (C.c_int, [_vp, C.POINTER(vrh_volume_stats)]),
+    "vrh_tex3d_host": (C.c_int, [C.POINTER(vrh_volume_desc), _vp, _u32, _vp]),
+    "vrh_tex1d_host": (C.c_int, [C.POINTER(vrh_transfunc_desc), _vp, _u32, _vp]),
+    "vrh_volume_render_host": (C.c_int, [C.POINTER(vrh_volume_desc), C.POINTER(vrh_transfunc_desc), C.POINTER(vrh_camera),
+                                         C.POINTER(vrh_volume_kernel_desc), _vp, _vp, _vp, _vp,
+                                         C.POINTER(vrh_volume_stats)]),
+    "vrh_volume_sample": (C.c_int, [_vp, _vp, _vp, _u32, _vp, _vp]),
 }
 
 _lib = None

@@ -212,6 +212,12 @@ class Context:
         t = buf.reshape(-1, 3).astype(np.float64)
         return (t - t[:, 0][t[:, 0] > 0].min()) / rate.value
 
+    def volume_last_stats(self):
+        """vrh_volume_last_stats: rays, steps and the capped flag of the last volume frame (waits for it)"""
+        s = capi.vrh_volume_stats()
+        capi.check("vrh_volume_last_stats", self.handle, C.byref(s))
+        return {"rays": s.rays, "steps": s.steps, "capped": s.capped}
+
     def stats_reset(self):
         capi.check("vrh_stats_reset", self.handle)
 
@@ -896,6 +902,152 @@ def pathtracing_kernel(bvh, shade, binding=normals_per_face_binding, bg=(0.0, 0.
     return k
 
 
+# ---- volume rendering (src/examples/volume/main.cpp) ---------------------------------------------
+
+_VOXEL_FORMATS = {np.dtype(np.uint8): capi.VRH_VOL_R8, np.dtype(np.uint16): capi.VRH_VOL_R16,
+                  np.dtype(np.float32): capi.VRH_VOL_R32F}
+
+
+def _address3(address):
+    return (int(address),) * 3 if np.isscalar(address) else tuple(int(a) for a in address)
+
+
+def volume_desc(voxels, filter=tex_filter.linear, address=tex_address.clamp):
+    """(vrh_volume_desc, the array it points into) of a (D, H, W) uint8 / uint16 / float32 array"""
+    vx = np.asarray(voxels)
+    if vx.ndim != 3 or vx.dtype not in _VOXEL_FORMATS:
+        raise TypeError("volume: a (D, H, W) uint8, uint16 or float32 array")
+    vx = np.ascontiguousarray(vx)
+    d = capi.vrh_volume_desc()
+    d.voxels = vx.ctypes.data if vx.size else None
+    d.depth, d.height, d.width = vx.shape
+    d.format, d.filter = _VOXEL_FORMATS[vx.dtype], int(filter)
+    d.address[:] = _address3(address)
+    return d, vx
+
+
+class transfunc:
+    """A transfer function <- texture_ref<vec4, 1>: `rgba` an (N, 4) float32 array, classified with the voxel
+    value as the coordinate."""
+
+    def __init__(self, rgba, filter=tex_filter.linear, address=tex_address.clamp):
+        a = np.ascontiguousarray(rgba, np.float32)
+        if a.ndim != 2 or a.shape[1] != 4:
+            raise TypeError("transfunc: an (N, 4) float32 array")
+        self.rgba, self.filter, self.address = a, int(filter), int(address)
+
+    def desc(self):
+        d = capi.vrh_transfunc_desc()
+        d.rgba = self.rgba.ctypes.data if self.rgba.size else None
+        d.size, d.filter, d.address = len(self.rgba), self.filter, self.address
+        return d
+
+    def tex1d(self, coords):
+        """tex1D of the reference at n coordinates on the host (vrh_tex1d_host): (n, 4) float32"""
+        c = np.ascontiguousarray(coords, np.float32).ravel()
+        out = np.zeros((len(c), 4), np.float32)
+        d = self.desc()
+        capi.check("vrh_tex1d_host", C.byref(d), _p(c), len(c), _p(out))
+        return out
+
+
+def tex3d_host(voxels, coords, filter=tex_filter.linear, address=tex_address.clamp):
+    """tex3D of the reference at (n, 3) coordinates on the host (vrh_tex3d_host): n float32"""
+    d, _keep = volume_desc(voxels, filter, address)
+    c = np.ascontiguousarray(coords, np.float32).reshape(-1, 3)
+    out = np.zeros(len(c), np.float32)
+    capi.check("vrh_tex3d_host", C.byref(d), _p(c), len(c), _p(out))
+    return out
+
+
+class volume:
+    """A scalar volume on the device with its transfer function <- texture_ref<float | unorm<8> | unorm<16>, 3>
+    and texture_ref<vec4, 1> of the volume example: `voxels` a (D, H, W) uint8 / uint16 / float32 array,
+    `address` one tex_address or (x, y, z).  Without a `transfunc` the volume starts with the linear ramp from
+    (0, 0, 0, 0) to (1, 1, 1, 1); set_transfunc replaces it."""
+
+    def __init__(self, ctx, voxels, filter=tex_filter.linear, address=tex_address.clamp, tf=None):
+        self.ctx = ctx
+        self.handle = None
+        d, _keep = volume_desc(voxels, filter, address)
+        tf = tf if tf is not None else transfunc([[0.0] * 4, [1.0] * 4])     # alive until the create call returns
+        td = tf.desc()
+        h = C.c_void_p()
+        capi.check("vrh_volume_create", ctx.handle, C.byref(d), C.byref(td), C.byref(h))
+        self.handle = h
+
+    def set_transfunc(self, tf):
+        """replaces the transfer function between two frames"""
+        td = tf.desc()
+        capi.check("vrh_volume_set_transfunc", self.handle, C.byref(td))
+
+    def sample(self, coords):
+        """the samplers on the device at (n, 3) coordinates: (tex3D values, tex1D of those values)"""
+        c = np.ascontiguousarray(coords, np.float32).reshape(-1, 3)
+        vox, rgba = np.zeros(len(c), np.float32), np.zeros((len(c), 4), np.float32)
+        capi.check("vrh_volume_sample", self.ctx.handle, self.handle, _p(c), len(c), _p(vox), _p(rgba))
+        return vox, rgba
+
+    def close(self):
+        if self.handle:
+            capi.lib().vrh_volume_free(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def float_not_below(x):
+    """the smallest float32 that is not below the double x: for a float w, w >= x holds exactly when
+    w >= that float (the example compares the opacity with the double 0.999)"""
+    f = np.float32(x)
+    return float(f if float(f) >= float(x) else np.nextafter(f, np.float32(np.inf)))
+
+
+def volume_kernel_desc(bbox, dt=0.01, opacity_cutoff=0.999, flip=(False, True, True)):
+    """vrh_volume_kernel_desc of a box ((min), (max)): axis d of the box maps onto [0, 1] of the texture,
+    reversed where flip[d] -- tc = (pos - min) / (max - min), or (max - pos) / (max - min)"""
+    bmin, bmax = (np.asarray(b, np.float32) for b in bbox)
+    k = capi.vrh_volume_kernel_desc()
+    for a in range(3):
+        k.box_min[a], k.box_max[a] = float(bmin[a]), float(bmax[a])
+        k.coord_sign[a] = -1.0 if flip[a] else 1.0
+        k.coord_offset[a] = float(bmax[a] if flip[a] else -bmin[a])
+        k.coord_extent[a] = float(np.float32(bmax[a] - bmin[a]))
+    k.dt = float(dt)
+    k.opacity_cutoff = float_not_below(opacity_cutoff)
+    return k
+
+
+class _volume_kernel:
+    def __init__(self, vol, desc):
+        self.volume = vol
+        self.desc = desc
+
+
+def volume_kernel(vol, bbox, dt=0.01, opacity_cutoff=0.999, flip=(False, True, True)):
+    """The kernel of the volume example (volume/main.cpp:123-167) over `vol` in the box `bbox`; the defaults
+    are the example's (box [-1, 1]^3: sign (1, -1, -1), offset 1, extent 2)."""
+    return _volume_kernel(vol, volume_kernel_desc(bbox, dt, opacity_cutoff, flip))
+
+
+def volume_render_host(voxels, tf, cam_basis, kdesc, filter=tex_filter.linear, address=tex_address.clamp):
+    """vrh_volume_render_host: the frame on the CPU -- colour, prim_id, t, steps per pixel and the stats"""
+    d, _keep = volume_desc(voxels, filter, address)
+    td = tf.desc()
+    n = cam_basis.width * cam_basis.height
+    out = {"color": np.zeros((n, 4), np.float32), "prim_id": np.zeros(n, np.uint32), "t": np.zeros(n, np.float32),
+           "steps_px": np.zeros(n, np.uint32)}
+    st = capi.vrh_volume_stats()
+    capi.check("vrh_volume_render_host", C.byref(d), C.byref(td), C.byref(cam_basis), C.byref(kdesc), _p(out["color"]),
+               _p(out["prim_id"]), _p(out["t"]), _p(out["steps_px"]), C.byref(st))
+    out["stats"] = {"rays": st.rays, "steps": st.steps, "capped": st.capped}
+    return out
+
+
 class hip_sched:
     """hip_sched<R>: drop-in for cuda_sched<R> (cuda_sched.h:25-40).
 
@@ -912,7 +1064,26 @@ class hip_sched:
         self.ctx = ctx
         ctx.set_option("async_frames", 1 if async_frames else 0)
 
+    def _volume_frame(self, kernel, sparams, shard, sync):
+        """the volume kernel (vrh_render_volume): uniform sampler, pinhole camera, whole image or scissor box"""
+        if getattr(sparams, "sampler", pixel_sampler.uniform_type).kind != pixel_sampler.uniform_type.kind:
+            raise ValueError("hip_sched::frame: the volume kernel takes the uniform pixel sampler only")
+        if getattr(sparams, "view_matrix", None) is not None:
+            raise ValueError("hip_sched::frame: the volume kernel takes a pinhole camera, not camera matrices")
+        if shard is not None:
+            raise ValueError("hip_sched::frame: the volume kernel renders no shards")
+        rt = sparams.rt
+        cam = sparams.cam.basis(*sparams.image_size)
+        if sparams.scissor_box is not None:
+            cam.scissor[:] = [int(v) for v in sparams.scissor_box]
+        rt.begin_frame()
+        capi.check("vrh_render_volume", self.ctx.handle, kernel.volume.handle, rt.handle, C.byref(cam), C.byref(kernel.desc))
+        if sync:
+            rt.end_frame()
+
     def frame(self, kernel, sparams, frame_num=0, shard=None, sync=True):
+        if isinstance(kernel, _volume_kernel):
+            return self._volume_frame(kernel, sparams, shard, sync)
         if not isinstance(kernel, _builtin_kernel):
             raise TypeError("hip_sched runs built-in kernels only (closest_hit / ao / simple / multi_hit / whitted / pathtracing): an "
                             "arbitrary "

@@ -73,6 +73,14 @@ struct vrh_ctx
     vrh::tuning_options opt;
     int opt_fused_widen = 0;        // VRH_OPT_FUSED_WIDEN (read by vrh_scene_upload)
     int opt_fused_step = 0;         // VRH_OPT_FUSED_STEP (read by vrh_scene_upload)
+    // the volume kernel (vrh_volume.hip): running device totals { steps, capped waves }, their copy in pinned host
+    // memory that every volume frame leaves behind it (not yet looked at while vol_pending), the totals before
+    // that frame, and the last frame's values (vrh_volume_last_stats)
+    unsigned long long* vol_counters = nullptr;
+    unsigned long long* vol_host = nullptr;
+    unsigned long long vol_base[2] = {};
+    bool vol_pending = false, vol_capped = false;
+    uint64_t vol_rays = 0, vol_steps = 0;
 };
 
 struct vrh_scene
@@ -188,6 +196,10 @@ inline hipError_t ctx_join(const vrh_ctx* ctx)
     if (any) ++ctx->join_epoch;
     return hipSuccess;
 }
+
+// after the context stream was waited for: reads the counters of a volume frame not yet looked at and reports
+// a frame that its step limit stopped, once (vrh_volume.hip)
+namespace vrh { int volume_collect(vrh_ctx* ctx); }
 
 // status plumbing shared by the C-ABI translation units: every HIP call is checked, nothing throws
 #define VRH_HIP(call)                                                                              \

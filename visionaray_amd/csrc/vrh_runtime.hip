@@ -149,6 +149,8 @@ VRH_API int vrh_ctx_destroy(vrh_ctx* ctx)
     }
     if (ctx->main_mark) (void)hipEventDestroy(ctx->main_mark);
     if (ctx->counters) (void)hipFree(ctx->counters);
+    if (ctx->vol_counters) (void)hipFree(ctx->vol_counters);
+    if (ctx->vol_host) (void)hipHostFree(ctx->vol_host);
     if (ctx->wave_times) (void)hipFree(ctx->wave_times);
     if (ctx->user_queues) (void)hipFree(ctx->user_queues);
     if (ctx->user_declined) (void)hipHostFree(ctx->user_declined);
@@ -1711,7 +1713,8 @@ VRH_API int vrh_sync(vrh_ctx* ctx)
     VRH_CHECK(ctx, "vrh_sync: null");
     VRH_HIP(hipSetDevice(ctx->device));
     for (hipEvent_t ev : ctx->group_written) VRH_HIP(hipEventSynchronize(ev));
-    return ctx_drain(ctx);
+    const int rc = ctx_drain(ctx);
+    return rc ? rc : volume_collect(ctx);
 }
 
 VRH_API int vrh_get_tile_times(vrh_ctx* ctx, uint64_t* out, uint64_t capacity, uint64_t* count)
@@ -1905,6 +1908,7 @@ VRH_API int vrh_rt_download(vrh_ctx* ctx, vrh_rt* rt, void* color, uint32_t* pri
     rc = rt_wait(ctx, rt);
     if (rc) return rc;
     VRH_HIP(hipStreamSynchronize(ctx->stream));
+    if ((rc = volume_collect(ctx))) return rc;      // a volume frame its step limit stopped is not delivered
     if (color) { VRH_CHECK(rt->color, "vrh_rt_download: target has no colour buffer"); VRH_HIP(hipMemcpy(color, rt->color, n * 16, hipMemcpyDeviceToHost)); }
     if (prim_id) { VRH_CHECK(rt->prim_id, "vrh_rt_download: target has no prim_id buffer"); VRH_HIP(hipMemcpy(prim_id, rt->prim_id, n * 4, hipMemcpyDeviceToHost)); }
     if (t) { VRH_CHECK(rt->t, "vrh_rt_download: target has no t buffer"); VRH_HIP(hipMemcpy(t, rt->t, n * 4, hipMemcpyDeviceToHost)); }

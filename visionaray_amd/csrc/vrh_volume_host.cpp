@@ -1,0 +1,127 @@
+// visionaray_amd/csrc/vrh_volume_host.cpp -- host entry points of the volume support (include/vrh.h):
+// vrh_tex3d_host, vrh_tex1d_host and vrh_volume_render_host, the host builds of the shared samplers and
+// march (visionaray_hip/detail/vrh_volume.h).
+#include "vrh_volhost.h"
+
+#include <new>
+
+using namespace vrh;
+
+namespace {
+
+// the voxels where they are, or an aligned copy when the pointer is not aligned for its format
+const void* aligned_voxels(const vrh_volume_desc& d, std::vector<uint32_t>& copy)
+{
+    const size_t b = voxel_bytes(d.format);
+    if ((reinterpret_cast<uintptr_t>(d.voxels) & (b - 1)) == 0) return d.voxels;
+    const size_t bytes = size_t(d.width) * d.height * d.depth * b;
+    copy.resize((bytes + 3) / 4);
+    std::memcpy(copy.data(), d.voxels, bytes);
+    return copy.data();
+}
+
+void copy_entries(const vrh_transfunc_desc& d, std::vector<dev::rgba_t>& out)
+{
+    out.resize(d.size);
+    std::memcpy(out.data(), d.rgba, size_t(d.size) * 16);
+}
+
+} // namespace
+
+extern "C" {
+
+VRH_API int vrh_tex3d_host(const vrh_volume_desc* desc, const float* coords, uint32_t n, float* out)
+{
+    if (!desc || (n && (!coords || !out))) { set_error("vrh_tex3d_host: null argument"); return VRH_ERR_INVALID; }
+    const std::string bad = check_volume_desc(*desc);
+    if (!bad.empty()) { set_error("vrh_tex3d_host: " + bad); return VRH_ERR_INVALID; }
+    const size_t bc = first_bad_coord(coords, size_t(n) * 3);
+    if (bc != size_t(n) * 3)
+    {
+        set_error("vrh_tex3d_host: coordinate " + std::to_string(bc / 3) + " is not finite or exceeds 2^20 in magnitude");
+        return VRH_ERR_INVALID;
+    }
+    try
+    {
+        std::vector<uint32_t> copy;
+        const dev::vol_view v = dev::make_vol_view(aligned_voxels(*desc, copy), desc->width, desc->height, desc->depth,
+                                                   desc->format, desc->filter, desc->address);
+        for (size_t i = 0; i < n; ++i) out[i] = dev::tex3d(v, coords[3 * i], coords[3 * i + 1], coords[3 * i + 2]);
+    }
+    catch (const std::bad_alloc&) { set_error("host allocation failed"); return VRH_ERR_OOM; }
+    return VRH_OK;
+}
+
+VRH_API int vrh_tex1d_host(const vrh_transfunc_desc* desc, const float* coords, uint32_t n, float* rgba_out)
+{
+    if (!desc || (n && (!coords || !rgba_out))) { set_error("vrh_tex1d_host: null argument"); return VRH_ERR_INVALID; }
+    const std::string bad = check_transfunc_desc(*desc);
+    if (!bad.empty()) { set_error("vrh_tex1d_host: " + bad); return VRH_ERR_INVALID; }
+    const size_t bc = first_bad_coord(coords, n);
+    if (bc != n)
+    {
+        set_error("vrh_tex1d_host: coordinate " + std::to_string(bc) + " is not finite or exceeds 2^20 in magnitude");
+        return VRH_ERR_INVALID;
+    }
+    try
+    {
+        std::vector<dev::rgba_t> entries;
+        copy_entries(*desc, entries);
+        const dev::tf_view t = dev::make_tf_view(entries.data(), desc->size, desc->filter, desc->address);
+        for (size_t i = 0; i < n; ++i)
+        {
+            const dev::rgba_t c = dev::tex1d(t, t.entries, coords[i]);
+            rgba_out[4 * i] = c.x; rgba_out[4 * i + 1] = c.y; rgba_out[4 * i + 2] = c.z; rgba_out[4 * i + 3] = c.w;
+        }
+    }
+    catch (const std::bad_alloc&) { set_error("host allocation failed"); return VRH_ERR_OOM; }
+    return VRH_OK;
+}
+
+VRH_API int vrh_volume_render_host(const vrh_volume_desc* vd, const vrh_transfunc_desc* td, const vrh_camera* cam,
+                                   const vrh_volume_kernel_desc* kd, float* color, uint32_t* prim_id, float* t,
+                                   uint32_t* steps_px, vrh_volume_stats* stats)
+{
+    if (!vd || !td || !cam || !kd) { set_error("vrh_volume_render_host: null argument"); return VRH_ERR_INVALID; }
+    std::string bad = check_volume_desc(*vd);
+    if (bad.empty()) bad = check_transfunc_desc(*td);
+    dev::march_params K{};
+    if (bad.empty()) bad = check_volume_kernel(*kd, *cam, K);
+    if (!bad.empty()) { set_error("vrh_volume_render_host: " + bad); return VRH_ERR_INVALID; }
+    try
+    {
+        std::vector<uint32_t> copy;
+        std::vector<dev::rgba_t> entries;
+        copy_entries(*td, entries);
+        const dev::vol_view vol = dev::make_vol_view(aligned_voxels(*vd, copy), vd->width, vd->height, vd->depth, vd->format,
+                                                     vd->filter, vd->address);
+        const dev::tf_view tf = dev::make_tf_view(entries.data(), td->size, td->filter, td->address);
+        uint32_t clip[4];
+        volume_clip(*cam, clip);
+        const float wf = float(cam->width), hf = float(cam->height);
+        vrh_volume_stats st{};
+        for (uint32_t y = clip[1]; y < clip[3]; ++y)
+            for (uint32_t x = clip[0]; x < clip[2]; ++x)
+            {
+                float dir[3], tnear, tfar;
+                dev::pinhole_dir(dir, cam->cam_u, cam->cam_v, cam->cam_w, x, y, wf, hf);
+                const bool hit = dev::box_clip(cam->eye, dir, K.bmin, K.bmax, tnear, tfar);
+                dev::rgba_t c;
+                bool capped;
+                const uint32_t steps = dev::march(vol, tf, tf.entries, K, cam->eye, dir, tnear, tfar, c, capped);
+                const size_t o = size_t(y) * cam->width + x;
+                if (color) { color[4 * o] = c.x; color[4 * o + 1] = c.y; color[4 * o + 2] = c.z; color[4 * o + 3] = c.w; }
+                if (prim_id) prim_id[o] = hit ? 0u : 0xFFFFFFFFu;
+                if (t) t[o] = hit ? tnear : -1.0f;
+                if (steps_px) steps_px[o] = steps;
+                st.rays += 1;
+                st.steps += steps;
+                st.capped |= capped ? 1u : 0u;
+            }
+        if (stats) *stats = st;
+    }
+    catch (const std::bad_alloc&) { set_error("host allocation failed"); return VRH_ERR_OOM; }
+    return VRH_OK;
+}
+
+} // extern "C"
