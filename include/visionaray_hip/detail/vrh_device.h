@@ -38,8 +38,8 @@
                              // index order; 1: hf1M +0.7 %, hf10M equal, profiles/r04/ab/sorted_push/)
 #endif
 #ifndef VRH_QUAD_STEP
-#define VRH_QUAD_STEP 5      // the 4-wide any-hit step of the AO kernel, one bit per item (profiles/quad_step/,
-                             // profiles/fused_slab/):
+#define VRH_QUAD_STEP 197    // the 4-wide any-hit step of the AO kernel, one bit per item (profiles/quad_step/,
+                             // profiles/fused_slab/, profiles/never_hit/):
                              // 1: its pushes go to the LDS part of the stack only (a ray without LDS room
                              //    restarts on the binary records), 2: one branch-free group of three stores
                              //    (needs 1; off: slower than the guarded pushes it replaces, its selects and
@@ -54,7 +54,15 @@
                              //    are point boxes at +inf, which no finite ray passes, 32: (needs 8) where the
                              //    exact box is tested: fetched with the leaf's triangles and tested before them
                              //    (off: fetched through the leaf-slot index and tested only after a hit, whose
-                             //    two dependent loads cost more than the fused test saves: -1 % against +0.8 %)
+                             //    two dependent loads cost more than the fused test saves: -1 % against +0.8 %),
+                             // 64: no compare of the exact records' links against QUAD_NONE in the AO kernel's
+                             //    step -- the upload of the same build writes their unused entries as point boxes
+                             //    at +inf (vrh_quad.cpp), which no finite ray passes; off: the
+                             //    unused entries repeat entry 0's box and the step compares, as libvrh_fused.so does,
+                             // 128: the AO kernel's overflow-stack instances form the stack's LDS limit from the
+                             //    argument segment before every step (vrh_kernels.hip kernarg_stack_cap) instead
+                             //    of holding it through the refill loop, where it was spilled to a VGPR lane and
+                             //    read back once per record by the 4-wide loop's room test (profiles/never_hit/)
 #endif
 #ifndef VRH_PACKED_SLABS
 #define VRH_PACKED_SLABS 0   // 1: slab distances with v_pk_add_f32 / v_pk_mul_f32
@@ -643,10 +651,13 @@ __device__ __forceinline__ int ray_step(const float4* __restrict__ pairs, const 
             }
             else
             {
-                h0 = quad_entry<FIN>(xl.x, yl.x, zl.x, xh.x, yh.x, zh.x, r, max_t, d0) & (k0 != QUAD_NONE);
-                h1 = quad_entry<FIN>(xl.y, yl.y, zl.y, xh.y, yh.y, zh.y, r, max_t, d1) & (k1 != QUAD_NONE);
-                h2 = quad_entry<FIN>(xl.z, yl.z, zl.z, xh.z, yh.z, zh.z, r, max_t, d2) & (k2 != QUAD_NONE);
-                h3 = quad_entry<FIN>(xl.w, yl.w, zl.w, xh.w, yh.w, zh.w, r, max_t, d3) & (k3 != QUAD_NONE);
+                // NEVER_HIT: the AO kernel's exact records hold a point box at +inf in every unused entry (vrh_quad.cpp,
+                // uploaded by the same build), which quad_entry fails for every finite ray -- tn = +inf, or tf = -inf
+                constexpr bool NEVER_HIT = QUAD_AO && (VRH_QUAD_STEP & 64) != 0;
+                h0 = quad_entry<FIN>(xl.x, yl.x, zl.x, xh.x, yh.x, zh.x, r, max_t, d0) & (NEVER_HIT || k0 != QUAD_NONE);
+                h1 = quad_entry<FIN>(xl.y, yl.y, zl.y, xh.y, yh.y, zh.y, r, max_t, d1) & (NEVER_HIT || k1 != QUAD_NONE);
+                h2 = quad_entry<FIN>(xl.z, yl.z, zl.z, xh.z, yh.z, zh.z, r, max_t, d2) & (NEVER_HIT || k2 != QUAD_NONE);
+                h3 = quad_entry<FIN>(xl.w, yl.w, zl.w, xh.w, yh.w, zh.w, r, max_t, d3) & (NEVER_HIT || k3 != QUAD_NONE);
             }
             if (COUNT) cnt.box += 4;
             if (!(h0 | h1 | h2 | h3)) return st.empty() ? -1 : 0;

@@ -43,6 +43,8 @@ constexpr uint32_t QUAD_NONE = 0xFFFFFFFFu;     // unused entry of a 4-wide reco
 // boxes widened for ray origins within `omax` (and by at least `extra`), and per leaf-ordered primitive the
 // entry (record * 4 + entry) of `out` that holds its leaf's exact box.  Built only if every node's box is valid
 // and lies inside its parent's; `out` does not depend on it.
+// `never_hit_unused`: the boxes of unused entries (link QUAD_NONE) in `out` are point boxes at +inf, which no ray
+// with finite origin and inverse direction passes, instead of copies of entry 0's box.
 struct fused_records
 {
     float omax = 0.0f, extra = 0.0f;              // in
@@ -52,7 +54,7 @@ struct fused_records
     bool built = false;                           // out
 };
 bool build_quads(const node32* nodes, uint32_t num_nodes, std::vector<float>& out, uint32_t& root_link,
-                 uint32_t& quad_depth, fused_records* fz = nullptr);
+                 uint32_t& quad_depth, fused_records* fz = nullptr, bool never_hit_unused = false);
 
 int build_bvh(const void* prims, uint32_t n, uint32_t kind, node32* nodes_out, uint32_t* num_nodes_out,
               uint32_t* indices_out, uint32_t* max_depth_out);

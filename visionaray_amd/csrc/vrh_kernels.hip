@@ -73,6 +73,8 @@ constexpr uint32_t TAG_NONFINITE = 0x80000000u;   // AO kernel lane tag: the ray
 // being held in a register across the refill loop, where the register allocator of the 6-wave AO
 // instances copied it to a VGPR and spilled that to scratch
 __device__ __forceinline__ uint32_t kernarg_root();
+// the same for the LDS entries of the stack (VRH_QUAD_STEP & 128)
+__device__ __forceinline__ uint32_t kernarg_stack_cap();
 
 __device__ __forceinline__ uint32_t lds_ld(const uint32_t* p)
 {
@@ -636,6 +638,12 @@ __device__ __forceinline__ uint32_t kernarg_root()
     typedef const volatile __attribute__((address_space(4))) uint32_t karg_u32;
     karg_u32* ka = (karg_u32*)__builtin_amdgcn_kernarg_segment_ptr();
     return ka[offsetof(render_params, root) / 4u];
+}
+__device__ __forceinline__ uint32_t kernarg_stack_cap()
+{
+    typedef const volatile __attribute__((address_space(4))) uint32_t karg_u32;
+    karg_u32* ka = (karg_u32*)__builtin_amdgcn_kernarg_segment_ptr();
+    return ka[offsetof(render_params, stack_cap) / 4u];
 }
 
 // One refilling loop per wave.  Primary rays (one per pixel of the wave's tile)
@@ -1229,6 +1237,10 @@ __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params 
                 // 4-wide ray here is an AO ray, its max_t the radius that quad_ok found <= FLT_MAX (a list
                 // of BVHs has no 4-wide records: its instances keep the plain call)
                 const float mt = VRH_AO_LEAN ? (any ? P.radius : FMAX) : max_t;
+                // VRH_QUAD_STEP & 128: the LDS limit of the overflow stack is formed here from the argument segment,
+                // so that the 4-wide loop's room test finds it in a scalar register instead of reloading a spilled one
+                // (the same value init() formed; not in the tail-sharing instances, which it costs VGPR spills)
+                if constexpr (SPILL && !COUNT && !LIST && !SHARE && (VRH_QUAD_STEP & 128) != 0) st.cap_off = kernarg_stack_cap() * block;
                 rc = (P.fast_ok && __ballot((tag & TAG_NONFINITE) != 0u) == 0ull)
                     ? ray_step<KIND, COUNT, true, false, void, AO_CAPPED, !LIST>(P.pairs, P.prims, LIST ? P.quads : P.aoquads, 0u, quad, r, mt, any, st, best_t, best_prim, cnt, steps, P.step_limit, resume, P.descent_cap, P.step_flags, nullptr, static_cast<const void*>(nullptr), hm, P.quads, P.leaf_slot)
                     : ray_step<KIND, COUNT, false, false, void, AO_CAPPED, !LIST>(P.pairs, P.prims, LIST ? P.quads : P.aoquads, 0u, quad, r, mt, any, st, best_t, best_prim, cnt, steps, P.step_limit, resume, P.descent_cap, P.step_flags, nullptr, static_cast<const void*>(nullptr), hm, P.quads, P.leaf_slot);

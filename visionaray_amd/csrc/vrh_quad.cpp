@@ -16,7 +16,9 @@
 //
 // Record (32 floats, 128 B): xmin[4] ymin[4] zmin[4] xmax[4] ymax[4] zmax[4] link[4] pad[4];
 // link = quad index of an inner grandchild, LEAF_BIT | first primitive (leaf order) of a leaf,
-// QUAD_NONE for an unused entry.
+// QUAD_NONE for an unused entry.  An unused entry's box repeats entry 0's, or with `never_hit_unused` (the
+// default build's upload, VRH_QUAD_STEP & 64) is the point box lo = hi = +inf that no finite ray passes, so the
+// AO kernel's step needs no compare of the link; every other reader of the records keeps its link test.
 #include "vrh_internal.h"
 #include "../../include/visionaray_hip/detail/vrh_fused_slab.h"
 
@@ -67,7 +69,7 @@ bool nested(const node32* nodes, uint32_t num_nodes)
 } // namespace
 
 bool build_quads(const node32* nodes, uint32_t num_nodes, std::vector<float>& out, uint32_t& root_link,
-                 uint32_t& quad_depth, fused_records* fz)
+                 uint32_t& quad_depth, fused_records* fz, bool never_hit_unused)
 {
     out.clear();
     quad_depth = 0;
@@ -145,8 +147,12 @@ bool build_quads(const node32* nodes, uint32_t num_nodes, std::vector<float>& ou
             const node32& b = nodes[used ? entries[e] : entries[0]];
             for (int a = 0; a < 3; ++a)
             {
-                rec[a * 4 + e] = b.bmin[a];
-                rec[12 + a * 4 + e] = b.bmax[a];
+                // never_hit_unused: a point box at +inf.  For a finite origin and a finite inverse direction
+                // (inf - o) * inv is +inf or -inf on every axis, never NaN: tn = +inf fails tn < max_t, or all
+                // axes give -inf and tf = -inf fails tf >= 0.  Not lo = +inf, hi = -inf:
+                // that box gives tn = -inf, tf = +inf and passes
+                rec[a * 4 + e] = (used || !never_hit_unused) ? b.bmin[a] : INFINITY;
+                rec[12 + a * 4 + e] = (used || !never_hit_unused) ? b.bmax[a] : INFINITY;
             }
             const uint32_t l = used ? links[e] : QUAD_NONE;
             std::memcpy(&rec[24 + e], &l, 4);

@@ -436,7 +436,9 @@ VRH_API int vrh_scene_upload(vrh_ctx* ctx, const void* nodes_v, uint32_t num_nod
         fz.extra = ctx->opt_fused_widen ? std::ldexp(extent, -ctx->opt_fused_widen) : 0.0f;
         fz.num_indices = num_indices;
     }
-    const bool have_quads = finite_bounds && build_quads(nodes, num_nodes, quads, quad_root, quad_depth, want_fused ? &fz : nullptr);
+    // VRH_QUAD_STEP & 64: the AO kernel's step does not compare links with QUAD_NONE, so unused entries get never-hit boxes
+    const bool have_quads = finite_bounds && build_quads(nodes, num_nodes, quads, quad_root, quad_depth, want_fused ? &fz : nullptr,
+                                                         (VRH_QUAD_STEP & 64) != 0);
 
     int rc = select_device(ctx);
     if (rc) return rc;
