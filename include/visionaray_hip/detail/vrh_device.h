@@ -30,48 +30,28 @@
 #include "vrh_sampler.h"
 #include "vrh_fused_slab.h"
 
-#ifndef VRH_SCALAR_UNIFORM
-#define VRH_SCALAR_UNIFORM 1   // wave-uniform pair fetches through the scalar cache (ray_step)
-#endif
-#ifndef VRH_SORTED_PUSH
-#define VRH_SORTED_PUSH 1    // the 4-wide any-hit step pushes its other hit entries farthest first (0: in
-                             // index order; 1: hf1M +0.7 %, hf10M equal, profiles/r04/ab/sorted_push/)
-#endif
-#ifndef VRH_QUAD_STEP
-#define VRH_QUAD_STEP 197    // the 4-wide any-hit step of the AO kernel, one bit per item (profiles/quad_step/,
-                             // profiles/fused_slab/, profiles/never_hit/):
-                             // 1: its pushes go to the LDS part of the stack only (a ray without LDS room
-                             //    restarts on the binary records), 2: one branch-free group of three stores
-                             //    (needs 1; off: slower than the guarded pushes it replaces, its selects and
-                             //    stores issue also where no lane of the wave pushes), 4: no tn < FLT_MAX
-                             //    compare where the host checked the radius, 8: where the scene has the fused
-                             //    records (vrh_fused_slab.h) the rays walk those, one v_fma per slab distance, and
-                             //    a leaf counts only if its exact box passes the exact test (off: with 16 and 32
-                             //    +1.1 % over the parent but -0.9 % against this tree without it, and its mere
-                             //    presence in the kernel costs as much; libvrh_fused.so is the build with 8 + 16
-                             //    + 32 that the tests run), 16: (needs 8) no
-                             //    compare of the fused records' links against QUAD_NONE -- their unused entries
-                             //    are point boxes at +inf, which no finite ray passes, 32: (needs 8) where the
-                             //    exact box is tested: fetched with the leaf's triangles and tested before them
-                             //    (off: fetched through the leaf-slot index and tested only after a hit, whose
-                             //    two dependent loads cost more than the fused test saves: -1 % against +0.8 %),
-                             // 64: no compare of the exact records' links against QUAD_NONE in the AO kernel's
-                             //    step -- the upload of the same build writes their unused entries as point boxes
-                             //    at +inf (vrh_quad.cpp), which no finite ray passes; off: the
-                             //    unused entries repeat entry 0's box and the step compares, as libvrh_fused.so does,
-                             // 128: the AO kernel's overflow-stack instances form the stack's LDS limit from the
-                             //    argument segment before every step (vrh_kernels.hip kernarg_stack_cap) instead
-                             //    of holding it through the refill loop, where it was spilled to a VGPR lane and
-                             //    read back once per record by the 4-wide loop's room test (profiles/never_hit/)
-#endif
-#ifndef VRH_PACKED_SLABS
-#define VRH_PACKED_SLABS 0   // 1: slab distances with v_pk_add_f32 / v_pk_mul_f32
+// The AO kernel's 4-wide any-hit step (ray_step, QUAD_AO): its pushes go to the LDS part of the stack only (a ray
+// without LDS room restarts on the binary records), the other hit entries are pushed farthest first, and where
+// the host checked the radius no tn < FLT_MAX compare is made.  The measurements behind each choice, and the
+// arms that lost, are in DESIGN.md sections 3 and 8.
+// VRH_FUSED_STEP 1 (libvrh_fused.so only; measured slower): where the scene has the fused
+// records (vrh_fused_slab.h) the 4-wide rays walk those, one v_fma per slab distance and no link compare (their
+// unused entries are point boxes at +inf), and a leaf counts only if its exact box, fetched with the leaf's
+// triangles, passes the exact test before them.
+#ifndef VRH_FUSED_STEP
+#define VRH_FUSED_STEP 0
 #endif
 
 namespace vrh {
 namespace dev {
 
-constexpr bool SCALAR_UNIFORM = VRH_SCALAR_UNIFORM != 0;
+// What the default build has and the fused library has not -- that library is kept as it was measured and tested.
+// NEVER_HIT_UNUSED: the exact records' unused entries are never-hit boxes (point boxes at +inf, vrh_quad.cpp; DESIGN.md
+// section 4) and the AO step compares no link with QUAD_NONE; otherwise they repeat entry 0's box and the step compares.
+// KERNARG_STACK_CAP: the AO kernel's overflow-stack instances form the stack's LDS limit from the argument segment
+// before every step (vrh_kernels.hip kernarg_stack_cap) instead of holding it through the refill loop.
+constexpr bool NEVER_HIT_UNUSED = !VRH_FUSED_STEP;
+constexpr bool KERNARG_STACK_CAP = !VRH_FUSED_STEP;
 constexpr uint32_t LEAF_BIT = 0x80000000u;
 constexpr uint32_t END_BIT = 1u;
 constexpr int KIND_TRI = 0;
@@ -97,12 +77,11 @@ __device__ __forceinline__ f3 normalize(f3 v) { return v * (1.0f / __builtin_sqr
 
 struct ray_t { f3 ori, dir, inv; };
 
-typedef float f2 __attribute__((ext_vector_type(2)));   // packed fp32: v_pk_add_f32 / v_pk_mul_f32
+typedef float f2 __attribute__((ext_vector_type(2)));   // a (child 0, child 1) pair of slab distances
 
 // Both children of a pair: math/intersect.h:52-70 slab test + update_if.h:60-66,82-88 box
-// is_closer.  The slab distances (b - o) * inv of child 0 and child 1 are computed two at a time
-// with packed fp32 adds and multiplies; each half is the same IEEE single operation as the scalar
-// expression, so nothing changes numerically.
+// is_closer.  The slab distances (b - o) * inv of child 0 and child 1 are kept side by side, each
+// the scalar IEEE expression (written with v_pk_add_f32 / v_pk_mul_f32 they measured slower).
 //
 // FAST = false is the reference formulation literally: min/max are the ternaries of
 // math/detail/math.h:48-60 (v_cmp + v_cndmask pairs).  FAST = true uses v_min/v_max/v_min3/v_max3.
@@ -115,16 +94,6 @@ template <bool FAST>
 __device__ __forceinline__ void box_pair(float4 q0, float4 q1, float4 q2, const ray_t& r, float best_t,
                                          float max_t, bool& b0, bool& b1, float& tn0, float& tn1)
 {
-#if VRH_PACKED_SLABS
-    const f2 ox = { r.ori.x, r.ori.x }, oy = { r.ori.y, r.ori.y }, oz = { r.ori.z, r.ori.z };
-    const f2 ix = { r.inv.x, r.inv.x }, iy = { r.inv.y, r.inv.y }, iz = { r.inv.z, r.inv.z };
-    const f2 t1x = (f2{ q0.x, q0.y } - ox) * ix;
-    const f2 t1y = (f2{ q0.z, q0.w } - oy) * iy;
-    const f2 t1z = (f2{ q1.x, q1.y } - oz) * iz;
-    const f2 t2x = (f2{ q1.z, q1.w } - ox) * ix;
-    const f2 t2y = (f2{ q2.x, q2.y } - oy) * iy;
-    const f2 t2z = (f2{ q2.z, q2.w } - oz) * iz;
-#else
     f2 t1x, t1y, t1z, t2x, t2y, t2z;
     t1x.x = (q0.x - r.ori.x) * r.inv.x; t1x.y = (q0.y - r.ori.x) * r.inv.x;
     t1y.x = (q0.z - r.ori.y) * r.inv.y; t1y.y = (q0.w - r.ori.y) * r.inv.y;
@@ -132,7 +101,6 @@ __device__ __forceinline__ void box_pair(float4 q0, float4 q1, float4 q2, const 
     t2x.x = (q1.z - r.ori.x) * r.inv.x; t2x.y = (q1.w - r.ori.x) * r.inv.x;
     t2y.x = (q2.x - r.ori.y) * r.inv.y; t2y.y = (q2.y - r.ori.y) * r.inv.y;
     t2z.x = (q2.z - r.ori.z) * r.inv.z; t2z.y = (q2.w - r.ori.z) * r.inv.z;
-#endif
     float tf0, tf1;
     if constexpr (FAST)
     {
@@ -311,27 +279,6 @@ struct stack_t
 #endif
             mem[base + used] = v;
         used += stride;
-    }
-    // m <= 3 pushes in one branch-free group (room_lds(3) holds): w0, w1, w2 are stored at the next three
-    // entries, of which the first m count -- the words above the new top are never read
-    __device__ __forceinline__ void push_lds3(uint32_t w0, uint32_t w1, uint32_t w2, uint32_t m)
-    {
-#if defined(__HIP_DEVICE_COMPILE__)
-        if constexpr (SPILL)
-        {
-            const uint32_t a = entry_addr();
-            *(lds_word*)uintptr_t(a) = w0;
-            *(lds_word*)uintptr_t(a + stride * 4u) = w1;
-            *(lds_word*)uintptr_t(a + stride * 8u) = w2;
-        }
-        else
-#endif
-        {
-            mem[base + used] = w0;
-            mem[base + used + stride] = w1;
-            mem[base + used + 2u * stride] = w2;
-        }
-        used += m * stride;
     }
     __device__ __forceinline__ uint32_t pop()
     {
@@ -514,8 +461,7 @@ __device__ __forceinline__ bool quad_entry(float xl, float yl, float zl, float x
 template <int KIND, bool COUNT, bool UV, class MultiList>
 __device__ __forceinline__ bool leaf_loop(const float4* __restrict__ prims, uint32_t link, const ray_t& r, float max_t,
                                           bool any, float& best_t, uint32_t& best_prim, test_counts& cnt,
-                                          hit_extra* hx, const MultiList* mh, const hit_mask_params* hm,
-                                          uint32_t* hit_index = nullptr)
+                                          hit_extra* hx, const MultiList* mh, const hit_mask_params* hm)
 {
     uint32_t i = link & ~LEAF_BIT;
     for (;;)
@@ -560,7 +506,7 @@ __device__ __forceinline__ bool leaf_loop(const float4* __restrict__ prims, uint
                 best_t = t;
                 best_prim = pid;
                 if constexpr (UV) { hx->u = hu; hx->v = hv; hx->li = i; }   // hit_record.h:54-64
-                if (any) { if (hit_index) *hit_index = i; return true; }   // exit_traversal.h:49-56
+                if (any) return true;                                      // exit_traversal.h:49-56
             }
         }
         if (flags & END_BIT) break;
@@ -588,12 +534,12 @@ __device__ __forceinline__ bool leaf_loop(const float4* __restrict__ prims, uint
 // CAPPED = false: an instance without the descent cap (`resume` is never set, `cap` is ignored): the
 // kernels whose launches never cap a descent keep no per-lane visit counter
 // QUAD_AO: the AO kernel's call -- the 4-wide rays' max_t is the AO radius, which the host found <= FLT_MAX
-// (render_params::quad_ok), and their pushes keep to the LDS part of the stack (VRH_QUAD_STEP).  With flags bit 2
-// `quads` are the fused records: the walk reaches a superset of the reference's leaves (the boxes are widened so
-// that the fused test never fails where the exact one passes), and a hit counts only if the exact box of its leaf --
-// entry leaf_slot[primitive] of `exact_quads` -- passes quad_entry; with every box inside its parent's that is
-// equivalent to the reference reaching the leaf, so the result is the reference's.  A rejected leaf is left like
-// one without a hit.
+// (render_params::quad_ok), and their pushes keep to the LDS part of the stack.  With flags bit 2 (VRH_FUSED_STEP
+// builds) `quads` are the fused records: the walk reaches a superset of the reference's leaves (the boxes are widened
+// so that the fused test never fails where the exact one passes), and a leaf counts only if its exact box --
+// leaf_boxes[2 x first primitive], fetched with its triangles -- passes quad_entry; with every box inside its parent's
+// that is equivalent to the reference reaching the leaf, so the result is the reference's.  A rejected leaf is left
+// like one without a hit, no load waits for one.
 template <int KIND, bool COUNT, bool FAST, bool UV = false, class MultiList = void, bool CAPPED = true, bool QUAD_AO = false, class Stack>
 __device__ __forceinline__ int ray_step(const float4* __restrict__ pairs, const float4* __restrict__ prims,
                                         const float4* __restrict__ quads, uint32_t root, bool& quad,
@@ -601,14 +547,13 @@ __device__ __forceinline__ int ray_step(const float4* __restrict__ pairs, const 
                                         float& best_t, uint32_t& best_prim, test_counts& cnt,
                                         uint32_t& steps, uint32_t step_limit, uint32_t& resume, uint32_t cap,
                                         uint32_t flags, hit_extra* hx = nullptr, const MultiList* mh = nullptr,
-                                        const hit_mask_params* hm = nullptr, const float4* __restrict__ exact_quads = nullptr,
-                                        const uint32_t* __restrict__ leaf_slot = nullptr)
+                                        const hit_mask_params* hm = nullptr, const float4* __restrict__ leaf_boxes = nullptr)
 {
-    constexpr bool FUSED = QUAD_AO && (VRH_QUAD_STEP & 8) != 0;
+    constexpr bool FUSED = QUAD_AO && VRH_FUSED_STEP != 0;
     const bool fz = FUSED && (flags & 4u) != 0u;       // wave-uniform
     // flags (render_params::step_flags): bit 0 pop on miss, bit 1 scalar fetch of wave-uniform pairs
     const bool pop_on_miss = (flags & 1u) != 0u;
-    const bool scalar_uniform = SCALAR_UNIFORM && (flags & 2u) != 0u;
+    const bool scalar_uniform = (flags & 2u) != 0u;
     // the tree was validated at upload (no cycles, links in range), so the descent terminates;
     // the guard below only bounds the number of outer iterations per ray
     uint32_t link;
@@ -636,24 +581,23 @@ __device__ __forceinline__ int ray_step(const float4* __restrict__ pairs, const 
             const uint32_t k0 = __float_as_uint(lk.x), k1 = __float_as_uint(lk.y);
             const uint32_t k2 = __float_as_uint(lk.z), k3 = __float_as_uint(lk.w);
             float d0, d1, d2, d3;
-            constexpr bool LDS_ONLY = QUAD_AO && (VRH_QUAD_STEP & 1) != 0;      // pushes without the overflow test
-            constexpr bool GROUP = LDS_ONLY && (VRH_QUAD_STEP & 2) != 0;        // ... as one branch-free group
-            constexpr bool FIN = QUAD_AO && (VRH_QUAD_STEP & 4) != 0;           // max_t <= FLT_MAX
+            constexpr bool LDS_ONLY = QUAD_AO;      // pushes without the overflow test
+            constexpr bool FIN = QUAD_AO;           // max_t <= FLT_MAX
             bool h0, h1, h2, h3;
             if constexpr (decltype(FZ)::value)
             {
-                constexpr bool INF_UNUSED = (VRH_QUAD_STEP & 16) != 0;
+                // no link compare: the fused records' unused entries are point boxes at +inf, which no finite ray passes
                 const float nx = -(r.ori.x * r.inv.x), ny = -(r.ori.y * r.inv.y), nz = -(r.ori.z * r.inv.z);
-                h0 = fused::entry<FIN>(xl.x, yl.x, zl.x, xh.x, yh.x, zh.x, r.inv.x, r.inv.y, r.inv.z, nx, ny, nz, max_t, d0) & (INF_UNUSED || k0 != QUAD_NONE);
-                h1 = fused::entry<FIN>(xl.y, yl.y, zl.y, xh.y, yh.y, zh.y, r.inv.x, r.inv.y, r.inv.z, nx, ny, nz, max_t, d1) & (INF_UNUSED || k1 != QUAD_NONE);
-                h2 = fused::entry<FIN>(xl.z, yl.z, zl.z, xh.z, yh.z, zh.z, r.inv.x, r.inv.y, r.inv.z, nx, ny, nz, max_t, d2) & (INF_UNUSED || k2 != QUAD_NONE);
-                h3 = fused::entry<FIN>(xl.w, yl.w, zl.w, xh.w, yh.w, zh.w, r.inv.x, r.inv.y, r.inv.z, nx, ny, nz, max_t, d3) & (INF_UNUSED || k3 != QUAD_NONE);
+                h0 = fused::entry<FIN>(xl.x, yl.x, zl.x, xh.x, yh.x, zh.x, r.inv.x, r.inv.y, r.inv.z, nx, ny, nz, max_t, d0);
+                h1 = fused::entry<FIN>(xl.y, yl.y, zl.y, xh.y, yh.y, zh.y, r.inv.x, r.inv.y, r.inv.z, nx, ny, nz, max_t, d1);
+                h2 = fused::entry<FIN>(xl.z, yl.z, zl.z, xh.z, yh.z, zh.z, r.inv.x, r.inv.y, r.inv.z, nx, ny, nz, max_t, d2);
+                h3 = fused::entry<FIN>(xl.w, yl.w, zl.w, xh.w, yh.w, zh.w, r.inv.x, r.inv.y, r.inv.z, nx, ny, nz, max_t, d3);
             }
             else
             {
                 // NEVER_HIT: the AO kernel's exact records hold a point box at +inf in every unused entry (vrh_quad.cpp,
                 // uploaded by the same build), which quad_entry fails for every finite ray -- tn = +inf, or tf = -inf
-                constexpr bool NEVER_HIT = QUAD_AO && (VRH_QUAD_STEP & 64) != 0;
+                constexpr bool NEVER_HIT = QUAD_AO && NEVER_HIT_UNUSED;
                 h0 = quad_entry<FIN>(xl.x, yl.x, zl.x, xh.x, yh.x, zh.x, r, max_t, d0) & (NEVER_HIT || k0 != QUAD_NONE);
                 h1 = quad_entry<FIN>(xl.y, yl.y, zl.y, xh.y, yh.y, zh.y, r, max_t, d1) & (NEVER_HIT || k1 != QUAD_NONE);
                 h2 = quad_entry<FIN>(xl.z, yl.z, zl.z, xh.z, yh.z, zh.z, r, max_t, d2) & (NEVER_HIT || k2 != QUAD_NONE);
@@ -671,7 +615,6 @@ __device__ __forceinline__ int ray_step(const float4* __restrict__ pairs, const 
             }
             // nearest hit entry first (ties -> lower index), the other hits pushed
             d0 = h0 ? d0 : INFINITY; d1 = h1 ? d1 : INFINITY; d2 = h2 ? d2 : INFINITY; d3 = h3 ? d3 : INFINITY;
-#if VRH_SORTED_PUSH
             // all hit entries in distance order: a 4-element sorting network, the nearest descended,
             // the others pushed farthest first.  Only the descended entry keeps the old selection's tie
             // rule (equal distances -> the lower index); the order among the pushed entries is not
@@ -686,31 +629,10 @@ __device__ __forceinline__ int ray_step(const float4* __restrict__ pairs, const 
                 const uint32_t u = sw ? kb : ka; kb = sw ? ka : kb; ka = u;
             };
             cx(e0, c0, e1, c1); cx(e2, c2, e3, c3); cx(e0, c0, e2, c2); cx(e1, c1, e3, c3); cx(e1, c1, e2, c2);
-            if constexpr (GROUP)
-            {
-                // the hit entries are a prefix e1..em of the sorted ones: the same stack content as the
-                // three guarded pushes below, without a branch (the words above the new top are not read)
-                const bool p2 = e2 != INFINITY, p3 = e3 != INFINITY;
-                const uint32_t m = uint32_t(e1 != INFINITY) + uint32_t(p2) + uint32_t(p3);
-                st.push_lds3(p3 ? c3 : p2 ? c2 : c1, p3 ? c2 : c1, c1, m);
-            }
-            else
-            {
-                if (e3 != INFINITY) push(c3);
-                if (e2 != INFINITY) push(c2);
-                if (e1 != INFINITY) push(c1);
-            }
+            if (e3 != INFINITY) push(c3);
+            if (e2 != INFINITY) push(c2);
+            if (e1 != INFINITY) push(c1);
             link = c0;
-#else
-            const bool a01 = d1 < d0, a23 = d3 < d2;
-            const float m01 = a01 ? d1 : d0, m23 = a23 ? d3 : d2;
-            const uint32_t j = (m23 < m01) ? (a23 ? 3u : 2u) : (a01 ? 1u : 0u);
-            if (h0 & (j != 0u)) push(k0);
-            if (h1 & (j != 1u)) push(k1);
-            if (h2 & (j != 2u)) push(k2);
-            if (h3 & (j != 3u)) push(k3);
-            link = j == 0u ? k0 : j == 1u ? k1 : j == 2u ? k2 : k3;
-#endif
         }
         return AT_LEAF;
     };
@@ -781,42 +703,20 @@ __device__ __forceinline__ int ray_step(const float4* __restrict__ pairs, const 
         }
         link = go0 ? l0 : l1;
     }
-    if constexpr (FUSED && (VRH_QUAD_STEP & 32) != 0)
+    if constexpr (FUSED)
         if (fz && quad)
         {
-            // placement (a): the leaf's exact box, keyed by its first primitive, is fetched with its triangles and
-            // tested before them -- a leaf the reference does not reach is left at once, no load waits for a hit
-            const float4* lb = reinterpret_cast<const float4*>(leaf_slot) + 2u * (link & ~LEAF_BIT);
+            // the leaf's exact box, keyed by its first primitive, is fetched with its triangles and tested before
+            // them -- a leaf the reference does not reach is left at once, no load waits for a hit
+            const float4* lb = leaf_boxes + 2u * (link & ~LEAF_BIT);
             const float4 lo = lb[0], hi = lb[1];
             if (COUNT) count_vmem(cnt, lb, 2u, VMEM_QUAD);
-            constexpr bool FIN = (VRH_QUAD_STEP & 4) != 0;
             float tn;
-            const bool reached = quad_entry<FIN>(lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, r, max_t, tn);
+            const bool reached = quad_entry<true>(lo.x, lo.y, lo.z, hi.x, hi.y, hi.z, r, max_t, tn);
             if (COUNT) { cnt.fz_checks += 1u; cnt.fz_rejects += reached ? 0u : 1u; }
             if (!reached) return st.empty() ? -1 : 0;
         }
-    uint32_t hit_index = 0u;
-    if (leaf_loop<KIND, COUNT, UV, MultiList>(prims, link, r, max_t, any, best_t, best_prim, cnt, hx, mh, hm,
-                                              (FUSED && !(VRH_QUAD_STEP & 32)) ? &hit_index : nullptr))
-    {
-        if constexpr (FUSED && !(VRH_QUAD_STEP & 32))
-            if (fz && quad)
-            {
-                // the hit was found through the widened boxes: it counts only if the reference reaches the leaf
-                const uint32_t slot = leaf_slot[hit_index];
-                const float* q = reinterpret_cast<const float*>(exact_quads) + 32u * (slot >> 2) + (slot & 3u);
-                constexpr bool FIN = (VRH_QUAD_STEP & 4) != 0;
-                float tn;
-                const bool reached = quad_entry<FIN>(q[0], q[4], q[8], q[12], q[16], q[20], r, max_t, tn);
-                if (COUNT) { cnt.fz_checks += 1u; cnt.fz_rejects += reached ? 0u : 1u; }
-                if (!reached)
-                {
-                    best_t = FMAX; best_prim = 0u;
-                    return st.empty() ? -1 : 0;
-                }
-            }
-        return 1;
-    }
+    if (leaf_loop<KIND, COUNT, UV, MultiList>(prims, link, r, max_t, any, best_t, best_prim, cnt, hx, mh, hm)) return 1;
     return st.empty() ? -1 : 0;
 }
 

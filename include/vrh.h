@@ -372,7 +372,7 @@ enum vrh_option {
                                     depth-first preorder, a pair's child-0 pair next to it in one
                                     128-B line; 2 = the builder's order (auto: 2; 1 measured
                                     neutral)                                                      */
-    VRH_OPT_FUSED_STEP = 28,     /* scene upload (read by vrh_scene_upload), builds with VRH_QUAD_STEP & 8 only
+    VRH_OPT_FUSED_STEP = 28,     /* scene upload (read by vrh_scene_upload), builds with VRH_FUSED_STEP only
                                     (libvrh_fused.so; the default build has no fused step and ignores it):
                                     2 = no fused 4-wide records for this scene, its AO rays take the exact
                                     4-wide step (auto, 1: records built where the tree nests)               */

@@ -1,5 +1,5 @@
 // tests/cpp/quad_unused_check.cpp -- the never-hit boxes of unused 4-wide entries (vrh_quad.cpp build_quads with
-// never_hit_unused, what the default build uploads; VRH_QUAD_STEP & 64), on the host.
+// never_hit_unused, what the default build uploads; vrh_device.h NEVER_HIT_UNUSED), on the host.
 //
 //   1. records: hand-made binary trees of 3, 5, 6 and 7 leaves (split in halves) and a comb of 6 leaves, whose
 //      4-wide records have 2, 3 and 4 children.  Every unused entry holds lo = hi = +inf on the three axes and the

@@ -1,5 +1,5 @@
 """GPU cases of the fused 4-wide records, run by tests/test_gpu_ao_fused.py in a process of its own that loads
-libvrh_fused.so (the build with the fused step compiled in, VRH_QUAD_STEP 8 + 16 + 32); not collected by name.
+libvrh_fused.so (the build with the fused step compiled in, VRH_FUSED_STEP); not collected by name.
 
 The AO kernel over the fused records (vrh_fused_slab.h: boxes widened at upload, one fma per slab distance, every
 leaf verified against its exact box) leaves every AO frame bit-identical to the oracle -- prim id, t bits, colour
@@ -142,7 +142,7 @@ def test_verification_runs_and_decides(ctx, widen):
     """Over the whole set of views and radii: leaves are checked against their exact boxes; at the exaggerated
     widenings some must be rejected.  (Measured, checks / rejects summed over the set: derived 948,663 / 335,
     eighth 56,676,376 / 56,589,295, half 496,283 / 492,838 -- at a half, most rays fill the LDS part of the stack
-    and restart on the binary records.  With the test after a hit instead, VRH_QUAD_STEP bit 32 off, no widening
+    and restart on the binary records.  With the test after a hit instead (measured and since removed), no widening
     gives a reject on these views: a ray that hits a triangle crosses the leaf's box, which contains it.)"""
     checks = rejects = 0
     for view in VIEWS:

@@ -1,6 +1,6 @@
 """GPU: the fused 4-wide records of the AO kernel (vrh_fused_slab.h).  They measured slower than the exact records
 (DESIGN.md section 8), so the default library is built without them and libvrh_fused.so with them
-(VRH_QUAD_STEP 8 + 16 + 32): the cases of tests/fused_cases.py -- every frame bit-identical to the oracle -- run
+(VRH_FUSED_STEP): the cases of tests/fused_cases.py -- every frame bit-identical to the oracle -- run
 in one child process that loads that library; the default library shows that it has no fused records."""
 import os
 import re

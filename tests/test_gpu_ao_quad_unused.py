@@ -1,4 +1,4 @@
-"""GPU: the AO kernel's 4-wide step without its link compares (VRH_QUAD_STEP bit 64).
+"""GPU: the AO kernel's 4-wide step without its link compares (vrh_device.h NEVER_HIT_UNUSED).
 
 The default build uploads every unused entry of a 4-wide record as a point box at +inf (vrh_quad.cpp), which no
 finite ray passes, and the AO kernel's step no longer compares the entries' links with QUAD_NONE.  Every AO frame

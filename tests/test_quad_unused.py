@@ -1,4 +1,4 @@
-"""The never-hit boxes of unused 4-wide entries (vrh_quad.cpp build_quads, VRH_QUAD_STEP bit 64) on the CPU --
+"""The never-hit boxes of unused 4-wide entries (vrh_quad.cpp build_quads, vrh_device.h NEVER_HIT_UNUSED) on the CPU --
 tests/cpp/quad_unused_check.cpp, host code built with AddressSanitizer and UBSan as a program of its own: every
 unused entry of hand-made trees' records is the point box at +inf with link QUAD_NONE, no admitted ray passes one
 under either form of the entry test without the link compare, every entry gives what the compared records gave,

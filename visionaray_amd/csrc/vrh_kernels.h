@@ -105,11 +105,11 @@ struct render_params
     float* mh_t;
     dev::hit_mask_params hmask;   // mask intersector (vrh_hit_mask), hmask.mask == null: none
     // the AO kernel's 4-wide records (appended: no other argument moves): `quads`, or with step_flags bit 2 the
-    // fused records over widened boxes (vrh_fused_slab.h) -- then a hit counts only if its leaf's exact box,
-    // entry leaf_slot[primitive] of `quads`, passes the exact test, and only rays with origins within fused_omax
+    // fused records over widened boxes (vrh_fused_slab.h) -- then a leaf counts only if its exact box,
+    // leaf_boxes[2 x first primitive], passes the exact test, and only rays with origins within fused_omax
     // use them
     const float4* aoquads;
-    const uint32_t* leaf_slot;
+    const float4* leaf_boxes;
     float fused_omax;
     float ao_reach;           // (eps + radius) * 1.001f in float: the AO reach of the tile cut (ao_cut_build)
 };

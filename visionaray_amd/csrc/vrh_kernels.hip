@@ -38,27 +38,10 @@ constexpr int AO_REC_WORDS = 4;                         // pos xyz, prim id (its
                                                         // 512 B less LDS per wave = 24 instead of 22 waves/CU)
 constexpr int AO_MASKS = 64 * AO_REC_WORDS;             // u32 masks[2][64]
 constexpr int AO_SLOT_PX = AO_MASKS + 2 * 64;           // u8 slot_px[2][64]: pixel (lane) of a hit slot
-#ifndef VRH_AO_CUT
-#define VRH_AO_CUT 1    // compile the AO entry cut in (render_params::ao_cut switches it per launch)
-#endif
-constexpr int AO_CUT = AO_SLOT_PX + 2 * 64 / 4;         // the current tile's entry cut (ao_cut_build)
-#ifndef VRH_AO_CUT_SPILL
-#define VRH_AO_CUT_SPILL 1   // 0: the cut only in the instances whose stack fits LDS (A/B)
-#endif
-#ifndef VRH_AO_CUT_MAX
-#define VRH_AO_CUT_MAX 8
-#endif
-// the AO kernel's lane state: 1 = max_t derived from `any` (AO rays: the radius, primaries: max())
-#ifndef VRH_AO_LEAN
-#define VRH_AO_LEAN 1
-#endif
-// 1 = the AO instances honour a descent cap (VRH_OPT_DESCENT_CAP; measured no gain on AO, round 4
-// profiles/r04/ab/cut16_dcap.log); 0 = compiled out (no `resume` / visit counter per lane)
-#ifndef VRH_AO_DCAP
-#define VRH_AO_DCAP 0
-#endif
-constexpr bool AO_CAPPED = VRH_AO_DCAP != 0;
-constexpr uint32_t CUT_MAX = VRH_AO_CUT_MAX;            // records of a cut
+constexpr int AO_CUT = AO_SLOT_PX + 2 * 64 / 4;         // the current tile's entry cut (ao_cut_build; compiled into
+                                                        // every non-LIST AO instance, render_params::ao_cut
+                                                        // switches it per launch)
+constexpr uint32_t CUT_MAX = 8;                         // records of a cut
 constexpr int AO_SH = AO_CUT + 2 * 8 * CUT_MAX;        // two levels x entries of box lo xyz, hi xyz, link, pad
 // Tail sharing (render_params::ao_share, blocks of several waves): once the tile queues are dry, a
 // wave publishes its last tile's AO rays in a header of its LDS area and hands them out through an
@@ -73,7 +56,7 @@ constexpr uint32_t TAG_NONFINITE = 0x80000000u;   // AO kernel lane tag: the ray
 // being held in a register across the refill loop, where the register allocator of the 6-wave AO
 // instances copied it to a VGPR and spilled that to scratch
 __device__ __forceinline__ uint32_t kernarg_root();
-// the same for the LDS entries of the stack (VRH_QUAD_STEP & 128)
+// the same for the LDS entries of the stack (KERNARG_STACK_CAP)
 __device__ __forceinline__ uint32_t kernarg_stack_cap();
 
 __device__ __forceinline__ uint32_t lds_ld(const uint32_t* p)
@@ -292,16 +275,10 @@ __device__ __forceinline__ uint32_t strip_lo(const render_params& P, uint32_t q,
     return (uint32_t)(((uint64_t)P.num_tiles * q) / nq);
 }
 
-#ifndef VRH_PRIMARY_CLUSTER
-#define VRH_PRIMARY_CLUSTER 1
-#endif
-// CLUSTER = false: an instance without the cluster order's code (its launches hand out the band order
-// for xcd_queues 3)
-template <bool CLUSTER = true>
 __device__ __forceinline__ uint32_t next_tile(const render_params& P, tile_queue& tq, uint32_t lane)
 {
     const uint32_t nq = P.xcd_queues ? 8u : 1u;
-    if (CLUSTER && P.xcd_queues == 3u)
+    if (P.xcd_queues == 3u)
     {
         // cluster order (frames in flight): queue q owns strip q of the launch's bands; a band is cut
         // into clusters of P.cluster tiles, and the units of a strip are (cluster, frame, tile) with
@@ -334,7 +311,7 @@ __device__ __forceinline__ uint32_t next_tile(const render_params& P, tile_queue
         }
         return NONE;
     }
-    if (P.xcd_queues == 2u || (!CLUSTER && P.xcd_queues == 3u))
+    if (P.xcd_queues == 2u)
     {
         // band-interleaved (frames in flight): the launch's (band, frame) units in band-major order,
         // unit u = band * num_frames + frame dealt to queue u % 8 -- all 8 XCDs sweep the image's
@@ -385,43 +362,25 @@ __device__ __forceinline__ uint32_t lane_rank(uint64_t mask)
 }
 
 // The AO hand-out path (start_ao: the idle lanes of a wave take new AO rays while the busy lanes'
-// rays stand still) is a latency chain; VRH_AO_HANDOUT's bits switch its shortenings for A/B builds
-// (every combination computes the same bits): 1 the disk sample is searched while
-// the hit record and the normal are in flight, 2 the search forms four candidates at a time
-// (vrh_sampler.h first_accepted_of16).  Reading the cut entries four at a time before testing them
-// measured slower and is not kept.
-// The tail-sharing and pixel-sampler instances keep the sequential path (HO = 0): at their register
+// rays stand still) is a latency chain, shortened in two ways (the same bits either
+// way): the disk sample is searched while the hit record and the normal are in flight, and the search forms
+// four candidates at a time (vrh_sampler.h first_accepted_of16).  Reading the cut entries four at a time
+// before testing them measured slower and is not kept.
+// The tail-sharing and pixel-sampler instances keep the sequential path (SHORT = false): at their register
 // budgets the shortened one cost a VGPR spill (sphere share instance) or scratch (sampler pass).
-#ifndef VRH_AO_HANDOUT
-#define VRH_AO_HANDOUT 3
-#endif
-constexpr uint32_t HO_REORDER = 1u, HO_SEARCH4 = 2u;
-
-template <uint32_t HO>
-__device__ __forceinline__ void handout_disk_sample(uint32_t p, uint32_t s, uint32_t salt, float& sx, float& sy)
-{
-    if (HO & HO_SEARCH4) { ao_disk_sample(p, s, salt, sx, sy); return; }
-    sx = 0.0f; sy = 0.0f;                                    // one candidate after the other
-    for (uint32_t k = 0; k < 16; ++k)
-    {
-        float xa, ya;
-        ao_disk_candidate(p, s, salt, k, xa, ya);
-        if (xa * xa + ya * ya < 1.0f) { sx = xa; sy = ya; break; }
-    }
-}
 
 // AO ray s of hit slot `slot` whose pixel has global index p in frame f of the launch
 // (ao/main.cpp:216-238 with the Appendix-A sampler, offset by the frame number)
-template <bool COUNT, uint32_t HO>
+template <bool COUNT, bool SHORT>
 __device__ __forceinline__ ray_t ao_ray(const render_params& P, const float* recs, uint32_t slot, uint32_t s,
                                         uint32_t p, uint32_t f, test_counts& cnt)
 {
-    // the slot's record (one aligned 16-B LDS read) and the gather of its normal are issued first and
-    // land while the disk sample is searched; the basis is formed after the search (HO_REORDER)
+    // SHORT: the slot's record (one aligned 16-B LDS read) and the gather of its normal are issued first and
+    // land while the disk sample is searched; the basis is formed after the search
     static_assert(AO_REC_WORDS == 4 && AO_WAVE_WORDS % 4 == 0, "a hit record is one aligned 16-B read");
     const float* sr = recs + slot * AO_REC_WORDS;
     float4 rec;
-    if constexpr ((HO & HO_REORDER) != 0u) rec = *reinterpret_cast<const float4*>(sr);
+    if constexpr (SHORT) rec = *reinterpret_cast<const float4*>(sr);
     else rec = make_float4(sr[0], sr[1], sr[2], sr[3]);
     f3 pos = mk3(rec.x, rec.y, rec.z);
     const float4* np = P.normals + __float_as_uint(rec.w);
@@ -429,12 +388,21 @@ __device__ __forceinline__ ray_t ao_ray(const render_params& P, const float* rec
     if (COUNT) count_vmem(cnt, np, 1u, VMEM_NORMAL);
     const uint32_t salt = frame_salt(P.frame_num + f);
     float sx = 0.0f, sy = 0.0f;
-    if (HO & HO_REORDER) handout_disk_sample<HO>(p, s, salt, sx, sy);
+    if (SHORT) ao_disk_sample(p, s, salt, sx, sy);
     f3 n = mk3(nn.x, nn.y, nn.z);
     // vector3.inl:357-367 make_orthonormal_basis(u, v, w = n)
     f3 bv = fabsf(n.x) > fabsf(n.y) ? normalize(mk3(-n.z, 0.0f, n.x)) : normalize(mk3(0.0f, n.z, -n.y));
     f3 bu = cross(bv, n);
-    if (!(HO & HO_REORDER)) handout_disk_sample<HO>(p, s, salt, sx, sy);
+    // (a function of its own: as a loop in this body it compiles to another instruction order in these instances)
+    if (!SHORT)
+        [&]() __attribute__((always_inline)) {
+            for (uint32_t k = 0; k < 16; ++k)                        // one candidate after the other
+            {
+                float xa, ya;
+                ao_disk_candidate(p, s, salt, k, xa, ya);
+                if (xa * xa + ya * ya < 1.0f) { sx = xa; sy = ya; return; }
+            }
+        }();
     f3 d = ao_direction(sx, sy, bu, bv, n);
     return make_ray(pos + d * P.eps, d);
 }
@@ -709,7 +677,7 @@ __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params 
     {
         // ---- primary visibility: stream pixels, write each when its ray finishes ------------
         tile_queue tq = queue_init(P);
-        uint32_t tile = next_tile<VRH_PRIMARY_CLUSTER != 0>(P, tq, lane);
+        uint32_t tile = next_tile(P, tq, lane);
         uint32_t handed = 0;                       // pixels of `tile` handed out (wave-uniform)
         uint32_t out_o = 0;
         hit_extra hx = { 0.0f, 0.0f, 0u };
@@ -732,7 +700,7 @@ __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params 
             {
                 if (handed >= 64u && tile != NONE)
                 {
-                    tile = next_tile<VRH_PRIMARY_CLUSTER != 0>(P, tq, lane);
+                    tile = next_tile(P, tq, lane);
                     handed = 0;
                 }
                 if (tile != NONE)
@@ -997,7 +965,7 @@ __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params 
         // own, which the 6-wave instances spilled
         // owner wave << 12 (the wave whose tile the ray belongs to: this one unless it helps a sibling)
         uint32_t tag = 0;
-        constexpr uint32_t HO = (SHARE || SAMPLED) ? 0u : uint32_t(VRH_AO_HANDOUT);   // hand-out path of this instance
+        constexpr bool SHORT_HANDOUT = !(SHARE || SAMPLED);       // hand-out path of this instance (ao_ray)
         // AO ray `cand` (slot-major: slot cand / S, sample cand % S) of the tile `tile` whose hit records,
         // slot pixels and cut are recs_ / spx / cut_, cutn (this wave's, or a sibling's it helps)
         auto start_ao = [&](const float* recs_, const uint8_t* spx, const float* cut_, uint32_t cutn, uint32_t tile,
@@ -1006,18 +974,18 @@ __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params 
             const uint32_t slot = (cand * P.samples_recip) >> 20, smp = cand - slot * S;
             uint32_t x, y, orow, fr;
             tile_pixel(P, tile, spx[par * 64u + slot], x, y, orow, fr);
-            r = ao_ray<COUNT, HO>(P, recs_, slot, smp, y * P.width + x, fr, cnt);
+            r = ao_ray<COUNT, SHORT_HANDOUT>(P, recs_, slot, smp, y * P.width + x, fr, cnt);
             best_t = FMAX; best_prim = 0; steps = 0; max_t = P.radius; any = true;
             bk = 0; res_t = FMAX; res_prim = 0;
             const bool fin = finite_ray(r);
             quad = P.quad_ok && fin;
             // the fused records serve rays that start within fused_omax (vrh_fused_slab.h ray_ok); any other ray
             // walks the binary records
-            if constexpr (!LIST && (VRH_QUAD_STEP & 8) != 0)
+            if constexpr (!LIST && VRH_FUSED_STEP != 0)
                 if (P.step_flags & 4u)
                     quad = quad && fused::ray_ok(r.ori.x, r.ori.y, r.ori.z, r.inv.x, r.inv.y, r.inv.z, P.fused_omax);
             st.reset(); resume = NO_RESUME;
-            if (!LIST && (!SPILL || VRH_AO_CUT_SPILL) && VRH_AO_CUT && quad && cutn != NONE)
+            if (!LIST && quad && cutn != NONE)
             {
                 // start at the tile's cut: the entries whose boxes this ray passes
 #pragma unroll 1
@@ -1032,14 +1000,12 @@ __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params 
                     tn = __builtin_fmaxf(tn, __builtin_fminf(t1, t2)); tf = __builtin_fminf(tf, __builtin_fmaxf(t1, t2));
                     t1 = (e[2] - r.ori.z) * r.inv.z; t2 = (e[5] - r.ori.z) * r.inv.z;
                     tn = __builtin_fmaxf(tn, __builtin_fminf(t1, t2)); tf = __builtin_fminf(tf, __builtin_fmaxf(t1, t2));
-                    // (VRH_QUAD_STEP: push_lds is unchecked.  Invariant: the stack is empty and cutn + 4 <= the
+                    // (push_lds is unchecked.  Invariant: the stack is empty and cutn + 4 <= the
                     // LDS entries -- every cutn that reaches here, this wave's cutN or a sibling's SH_CUTN, is
                     // the value the cut build clamped to NONE otherwise, and all waves of a block share one
                     // capacity.  A 4-wide ray's radius is <= FLT_MAX (plan_launch: quad_ok), so tn < max_t
                     // implies tn < FMAX)
-                    const bool pass = (VRH_QUAD_STEP & 4) ? (tf >= tn) & (tf >= 0.0f) & (tn < max_t)
-                                                          : (tf >= tn) & (tn < FMAX) & (tf >= 0.0f) & (tn < max_t);
-                    if (pass) { if constexpr ((VRH_QUAD_STEP & 1) != 0) st.push_lds(__float_as_uint(e[6])); else st.push(__float_as_uint(e[6])); }
+                    if ((tf >= tn) & (tf >= 0.0f) & (tn < max_t)) st.push_lds(__float_as_uint(e[6]));
                 }
                 if (COUNT) cnt.box += cutn;
             }
@@ -1121,8 +1087,7 @@ __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params 
                 const uint32_t avail = pubC * S;
                 // measured with entries nearest-first: hf1M +9 %, hf10M +4.8 %
                 // (profiles/r02_ab/ab32_*, ab33_*, ab34_ao_cut_spill.log)
-                constexpr bool CUT = !LIST && (!SPILL || VRH_AO_CUT_SPILL) && VRH_AO_CUT;
-                if constexpr (CUT)
+                if constexpr (!LIST)
                     if (P.ao_cut && issC == 0u)
                     {
                         // the tile's first AO hand-out: all its hits are published (ao_gate)
@@ -1235,15 +1200,16 @@ __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params 
                 // 4-wide descent at is pair 0: 4-wide records exist only for trees whose root is a pair,
                 // stored first (render_params::quad_ok checks it), so no register holds it.  QUAD_AO: a
                 // 4-wide ray here is an AO ray, its max_t the radius that quad_ok found <= FLT_MAX (a list
-                // of BVHs has no 4-wide records: its instances keep the plain call)
-                const float mt = VRH_AO_LEAN ? (any ? P.radius : FMAX) : max_t;
-                // VRH_QUAD_STEP & 128: the LDS limit of the overflow stack is formed here from the argument segment,
+                // of BVHs has no 4-wide records: its instances keep the plain call).  CAPPED = false: the descent cap
+                // (VRH_OPT_DESCENT_CAP) measured no gain on AO (profiles/r04/ab/cut16_dcap.log)
+                const float mt = any ? P.radius : FMAX;
+                // KERNARG_STACK_CAP: the LDS limit of the overflow stack is formed here from the argument segment,
                 // so that the 4-wide loop's room test finds it in a scalar register instead of reloading a spilled one
                 // (the same value init() formed; not in the tail-sharing instances, which it costs VGPR spills)
-                if constexpr (SPILL && !COUNT && !LIST && !SHARE && (VRH_QUAD_STEP & 128) != 0) st.cap_off = kernarg_stack_cap() * block;
+                if constexpr (SPILL && !COUNT && !LIST && !SHARE && KERNARG_STACK_CAP) st.cap_off = kernarg_stack_cap() * block;
                 rc = (P.fast_ok && __ballot((tag & TAG_NONFINITE) != 0u) == 0ull)
-                    ? ray_step<KIND, COUNT, true, false, void, AO_CAPPED, !LIST>(P.pairs, P.prims, LIST ? P.quads : P.aoquads, 0u, quad, r, mt, any, st, best_t, best_prim, cnt, steps, P.step_limit, resume, P.descent_cap, P.step_flags, nullptr, static_cast<const void*>(nullptr), hm, P.quads, P.leaf_slot)
-                    : ray_step<KIND, COUNT, false, false, void, AO_CAPPED, !LIST>(P.pairs, P.prims, LIST ? P.quads : P.aoquads, 0u, quad, r, mt, any, st, best_t, best_prim, cnt, steps, P.step_limit, resume, P.descent_cap, P.step_flags, nullptr, static_cast<const void*>(nullptr), hm, P.quads, P.leaf_slot);
+                    ? ray_step<KIND, COUNT, true, false, void, false, !LIST>(P.pairs, P.prims, LIST ? P.quads : P.aoquads, 0u, quad, r, mt, any, st, best_t, best_prim, cnt, steps, P.step_limit, resume, P.descent_cap, P.step_flags, nullptr, static_cast<const void*>(nullptr), hm, P.leaf_boxes)
+                    : ray_step<KIND, COUNT, false, false, void, false, !LIST>(P.pairs, P.prims, LIST ? P.quads : P.aoquads, 0u, quad, r, mt, any, st, best_t, best_prim, cnt, steps, P.step_limit, resume, P.descent_cap, P.step_flags, nullptr, static_cast<const void*>(nullptr), hm, P.leaf_boxes);
             }
             if constexpr (LIST)
                 if (busy && rc < 0) rc = list_next(P, any, bk, res_t, res_prim, best_t, best_prim, st, resume);
@@ -1312,7 +1278,7 @@ __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params 
     }
 
     // (the AO step loop's uncounted instances: a lane number formed anew, see flush_totals)
-    constexpr bool FRESH = AO && !COUNT && !LIST && (VRH_QUAD_STEP & 8) != 0;
+    constexpr bool FRESH = AO && !COUNT && !LIST && VRH_FUSED_STEP != 0;
     const uint32_t lane_end = FRESH ? lane_again() : __lane_id();
     if (wt_slot && lane_end == 0u) wt_slot[1] = wall_clock64();
     flush_totals<COUNT, AO, FRESH>(P, lane_end, rays_total, hits_total, cnt);

@@ -91,10 +91,10 @@ struct vrh_scene
     float4* normals = nullptr;
     float4* quads = nullptr;     // 4-wide any-hit records (vrh_quad.cpp), null if the scene has none
     // the fused records of the AO kernel's 4-wide step (vrh_quad.cpp fused_records): `quads` over widened boxes,
-    // and per leaf-ordered primitive the entry of `quads` with its leaf's exact box; null if the tree failed the
+    // and per leaf-ordered primitive its leaf's exact box (two float4); null if the tree failed the
     // nesting check (the AO rays then take the exact 4-wide step).  Valid for ray origins within fused_omax
     float4* fquads = nullptr;
-    uint32_t* leaf_slot = nullptr;
+    float4* leaf_boxes = nullptr;
     float fused_omax = 0.0f;
     float4* vnormals = nullptr;  // per-vertex normals (3 per prim_id), VRH_NORMALS_PER_VERTEX
     vrh::node32* dnodes = nullptr;    // GPU-built scenes: the tree in the reference layout (download)

@@ -17,8 +17,8 @@
 // Record (32 floats, 128 B): xmin[4] ymin[4] zmin[4] xmax[4] ymax[4] zmax[4] link[4] pad[4];
 // link = quad index of an inner grandchild, LEAF_BIT | first primitive (leaf order) of a leaf,
 // QUAD_NONE for an unused entry.  An unused entry's box repeats entry 0's, or with `never_hit_unused` (the
-// default build's upload, VRH_QUAD_STEP & 64) is the point box lo = hi = +inf that no finite ray passes, so the
-// AO kernel's step needs no compare of the link; every other reader of the records keeps its link test.
+// default build's upload, vrh_device.h NEVER_HIT_UNUSED) is the point box lo = hi = +inf that no finite ray passes, so
+// the AO kernel's step needs no compare of the link; every other reader of the records keeps its link test.
 #include "vrh_internal.h"
 #include "../../include/visionaray_hip/detail/vrh_fused_slab.h"
 

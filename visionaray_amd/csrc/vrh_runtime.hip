@@ -421,9 +421,9 @@ VRH_API int vrh_scene_upload(vrh_ctx* ctx, const void* nodes_v, uint32_t num_nod
     uint32_t quad_root = 0, quad_depth = 0;
     // the fused records (vrh_fused_slab.h) serve ray origins within twice the root box's largest coordinate: an
     // AO ray starts on a surface, inside the root box; a ray from farther out walks the binary records
-    // (only in a build whose kernels walk them, VRH_QUAD_STEP & 8 -- libvrh_fused.so; VRH_OPT_FUSED_STEP 2 leaves them out)
+    // (only in a build whose kernels walk them, VRH_FUSED_STEP -- libvrh_fused.so; VRH_OPT_FUSED_STEP 2 leaves them out)
     fused_records fz;
-    const bool want_fused = (VRH_QUAD_STEP & 8) != 0 && ctx->opt_fused_step != 2;
+    const bool want_fused = VRH_FUSED_STEP != 0 && ctx->opt_fused_step != 2;
     if (finite_bounds)
     {
         float extent = 0.0f;
@@ -436,9 +436,9 @@ VRH_API int vrh_scene_upload(vrh_ctx* ctx, const void* nodes_v, uint32_t num_nod
         fz.extra = ctx->opt_fused_widen ? std::ldexp(extent, -ctx->opt_fused_widen) : 0.0f;
         fz.num_indices = num_indices;
     }
-    // VRH_QUAD_STEP & 64: the AO kernel's step does not compare links with QUAD_NONE, so unused entries get never-hit boxes
+    // NEVER_HIT_UNUSED: the AO kernel's step does not compare links with QUAD_NONE, so unused entries get never-hit boxes
     const bool have_quads = finite_bounds && build_quads(nodes, num_nodes, quads, quad_root, quad_depth, want_fused ? &fz : nullptr,
-                                                         (VRH_QUAD_STEP & 64) != 0);
+                                                         vrh::dev::NEVER_HIT_UNUSED);
 
     int rc = select_device(ctx);
     if (rc) return rc;
@@ -470,25 +470,20 @@ VRH_API int vrh_scene_upload(vrh_ctx* ctx, const void* nodes_v, uint32_t num_nod
         bytes += qb;
         if (fz.built)
         {
-            // VRH_QUAD_STEP & 32: instead of the slots, the exact boxes themselves, two float4 per leaf-ordered primitive
-            std::vector<float> boxes;
-            if (VRH_QUAD_STEP & 32)
+            // the leaves' exact boxes, two float4 per leaf-ordered primitive (read at a leaf's first primitive)
+            std::vector<float> boxes(size_t(8) * fz.leaf_slot.size(), 0.0f);
+            for (size_t i = 0; i < fz.leaf_slot.size(); ++i)
             {
-                boxes.assign(size_t(8) * fz.leaf_slot.size(), 0.0f);
-                for (size_t i = 0; i < fz.leaf_slot.size(); ++i)
-                {
-                    const uint32_t s = fz.leaf_slot[i];
-                    if (s == QUAD_NONE) continue;
-                    const float* rec = &quads[size_t(s >> 2) * 32 + (s & 3u)];
-                    for (int a = 0; a < 3; ++a) { boxes[8 * i + a] = rec[4 * a]; boxes[8 * i + 4 + a] = rec[12 + 4 * a]; }
-                }
+                const uint32_t s = fz.leaf_slot[i];
+                if (s == QUAD_NONE) continue;
+                const float* rec = &quads[size_t(s >> 2) * 32 + (s & 3u)];
+                for (int a = 0; a < 3; ++a) { boxes[8 * i + a] = rec[4 * a]; boxes[8 * i + 4 + a] = rec[12 + 4 * a]; }
             }
-            const void* aux = (VRH_QUAD_STEP & 32) ? static_cast<const void*>(boxes.data()) : static_cast<const void*>(fz.leaf_slot.data());
-            const size_t sb = (VRH_QUAD_STEP & 32) ? boxes.size() * sizeof(float) : fz.leaf_slot.size() * sizeof(uint32_t);
+            const size_t sb = boxes.size() * sizeof(float);
             if ((e = hipMalloc(&sc->fquads, qb)) != hipSuccess) return fail(e, "hipMalloc(fused records)");
             if ((e = hipMemcpy(sc->fquads, fz.recs.data(), qb, hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "upload fused records");
-            if ((e = hipMalloc(&sc->leaf_slot, sb)) != hipSuccess) return fail(e, "hipMalloc(leaf slots)");
-            if ((e = hipMemcpy(sc->leaf_slot, aux, sb, hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "upload leaf slots");
+            if ((e = hipMalloc(&sc->leaf_boxes, sb)) != hipSuccess) return fail(e, "hipMalloc(leaf boxes)");
+            if ((e = hipMemcpy(sc->leaf_boxes, boxes.data(), sb, hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "upload leaf boxes");
             sc->fused_omax = fz.omax;
             sc->info.fused_records = sc->info.wide_records;
             sc->info.fused_bytes = qb + sb;       // not part of device_bytes, which the launch plan reads
@@ -551,7 +546,7 @@ VRH_API int vrh_scene_free(vrh_scene* sc)
     if (sc->normals) (void)hipFree(sc->normals);
     if (sc->quads) (void)hipFree(sc->quads);
     if (sc->fquads) (void)hipFree(sc->fquads);
-    if (sc->leaf_slot) (void)hipFree(sc->leaf_slot);
+    if (sc->leaf_boxes) (void)hipFree(sc->leaf_boxes);
     if (sc->vnormals) (void)hipFree(sc->vnormals);
     if (sc->dnodes) (void)hipFree(sc->dnodes);
     if (sc->dindices) (void)hipFree(sc->dindices);
@@ -1392,9 +1387,9 @@ int plan_render(const vrh_ctx* ctx, const vrh_scene* sc, uint32_t num_frames, co
     in.device_bytes = sc->info.device_bytes;
     in.finite_bounds = sc->finite_bounds; in.has_quads = sc->quads != nullptr; in.root_is_pair0 = sc->roots[0] == 0u;
     in.opt = ctx->opt;
-    // the AO kernel's 4-wide step leaves out the tn < FLT_MAX compare that tn < radius implies
-    // (VRH_QUAD_STEP & 4): an AO radius that is not <= FLT_MAX (inf, NaN) walks the binary records instead
-    in.radius_finite = !(VRH_QUAD_STEP & 4) || k->kind != VRH_KERNEL_AO || k->radius <= FLT_MAX;
+    // the AO kernel's 4-wide step leaves out the tn < FLT_MAX compare that tn < radius implies:
+    // an AO radius that is not <= FLT_MAX (inf, NaN) walks the binary records instead
+    in.radius_finite = k->kind != VRH_KERNEL_AO || k->radius <= FLT_MAX;
     std::string err;
     const int rc = plan_launch(in, render_device{}, plan, err);
     if (rc) set_error(err);
@@ -1417,13 +1412,13 @@ int fill_params(render_params& p, const launch_plan& plan, const vrh_ctx* ctx, c
     p.stack_cap = uint32_t(plan.cfg.stack_cap); p.stack_total = plan.stack_total; p.quad_lds = plan.quad_lds;
     p.fast_ok = plan.fast_ok;
     p.quads = sc->quads; p.quad_ok = plan.quad_ok;
-    // the AO kernel's 4-wide rays walk the fused records where the scene has them (VRH_QUAD_STEP & 8): step_flags
-    // bit 2, and the exact records stay at hand for the verification of a hit
-    p.aoquads = sc->quads; p.leaf_slot = nullptr; p.fused_omax = 0.0f;
+    // the AO kernel's 4-wide rays walk the fused records where the scene has them (VRH_FUSED_STEP): step_flags
+    // bit 2, and the leaves' exact boxes go with them
+    p.aoquads = sc->quads; p.leaf_boxes = nullptr; p.fused_omax = 0.0f;
     p.ao_reach = (k->eps + k->radius) * 1.001f;
-    if ((VRH_QUAD_STEP & 8) && ao && plan.quad_ok && sc->fquads && sc->num_roots == 1)
+    if (VRH_FUSED_STEP && ao && plan.quad_ok && sc->fquads && sc->num_roots == 1)
     {
-        p.aoquads = sc->fquads; p.leaf_slot = sc->leaf_slot; p.fused_omax = sc->fused_omax;
+        p.aoquads = sc->fquads; p.leaf_boxes = sc->leaf_boxes; p.fused_omax = sc->fused_omax;
         p.step_flags |= 4u;
     }
     p.ao_cut = plan.ao_cut; p.ao_share = plan.ao_share;
