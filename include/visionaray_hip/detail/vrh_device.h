@@ -17,6 +17,9 @@
 //            primitive of each leaf carries END_BIT.  triangle = 3 x float4 (48 B):
 //              (v1.xyz, e1.x) (e1.yz, e2.xy) (e2.z, prim_id, geom_id, flags)
 //            sphere = 2 x float4 (32 B): (center.xyz, radius) (prim_id, geom_id, flags, 0)
+//            generic (triangles and spheres in one list, VRH_PRIM_GENERIC80) = the triangle's 3 x float4; a
+//            sphere keeps (center.xyz, radius) in the first, both kinds (prim_id, geom_id, flags) in the last
+//            three words of the third, and SPHERE_BIT of the flags word says which of the two the record is
 //   normals: float4 per prim_id (face normals for AO, get_normal.h:26-37).
 //
 // Arithmetic is the reference's, operation for operation (compiled with -ffp-contract=off and
@@ -56,6 +59,8 @@ constexpr uint32_t LEAF_BIT = 0x80000000u;
 constexpr uint32_t END_BIT = 1u;
 constexpr int KIND_TRI = 0;
 constexpr int KIND_SPHERE = 1;
+constexpr int KIND_GENERIC = 2;                 // leaf_loop / ray_step only: no instance_key has it (vrh_launch.h)
+constexpr uint32_t SPHERE_BIT = 2u;             // flags word of a generic record: the record is a sphere
 constexpr float FMAX = 3.402823466e+38f;       // numeric_limits<float>::max(), hit_record ctor
 
 // math/detail/math.h:48-60
@@ -477,6 +482,20 @@ __device__ __forceinline__ bool leaf_loop(const float4* __restrict__ prims, uint
             h = isect_tri(r, a, b, c, t, hu, hv);
             pid = __float_as_uint(c.y);
             flags = __float_as_uint(c.w);
+        }
+        else if constexpr (KIND == KIND_GENERIC)
+        {
+            // generic_primitive<triangle, sphere>: the record's type bit picks the test, per lane (a wave whose
+            // lanes all sit on one kind runs that test only; both tests computed and selected would cost every
+            // wave the sphere's IEEE square root and two divisions on top of the triangle's division, and keep
+            // both results live -- DESIGN.md section 3).  hu / hv stay 0 for a sphere (its hit record has none).
+            const float4* q = prims + 3u * i;
+            float4 a = q[0], b = q[1], c = q[2];
+            if (COUNT) { count_vmem(cnt, q); count_vmem(cnt, q + 1); count_vmem(cnt, q + 2); }
+            pid = __float_as_uint(c.y);
+            flags = __float_as_uint(c.w);
+            if (flags & SPHERE_BIT) h = isect_sphere(r, a, t);
+            else h = isect_tri(r, a, b, c, t, hu, hv);
         }
         else
         {

@@ -96,6 +96,43 @@ template <typename T> struct is_triangle<T, decltype((void)std::declval<T>().e2)
 
 // sched_params::scissor_box (scheduler.h:25-31; make_sched_params sets recti(0, 0, w, h), :175),
 // read as cuda_sched reads it (cuda_sched.inl:71): x <= px < w, y <= py < h
+// generic_primitive<basic_triangle<3, float>, basic_sphere<float>> (the reference's, or standalone.h's stand-in): a
+// variant of exactly those two alternatives, in that order -- the record VRH_PRIM_GENERIC80 takes verbatim
+template <typename T> struct is_generic_primitive : std::false_type {};
+template <template <typename...> class GP, typename A, typename B>
+struct is_generic_primitive<GP<A, B>> : std::integral_constant<bool, is_triangle<A>::value && is_sphere<B>::value>
+{
+    using triangle_type = A;
+    using sphere_type = B;
+};
+// vrh_prim_kind and record size of a primitive type
+template <typename P> constexpr uint32_t prim_kind_of()
+{
+    return is_generic_primitive<P>::value ? uint32_t(VRH_PRIM_GENERIC80) : is_sphere<P>::value ? uint32_t(VRH_PRIM_SPHERE48) : uint32_t(VRH_PRIM_TRI64);
+}
+template <typename P> constexpr size_t prim_bytes_of() { return is_generic_primitive<P>::value ? 80 : is_sphere<P>::value ? 48 : 64; }
+// The type index of a generic record sits at byte VRH_GENERIC_TYPE_OFFSET: 1 for the triangle, 2 for the sphere.  A
+// variant keeps it private, so the offset is checked on a probe of each alternative where a BVH is constructed.
+template <typename P>
+inline typename std::enable_if<is_generic_primitive<P>::value>::type check_record_layout()
+{
+    static_assert(sizeof(P) == 80 && alignof(P) == 16, "generic_primitive<triangle, sphere> must be the 80-byte record, aligned to 16");
+    static_assert(sizeof(typename is_generic_primitive<P>::triangle_type) == 64 && sizeof(typename is_generic_primitive<P>::sphere_type) == 48,
+                  "the alternatives must be basic_triangle<3,float> (64 B) and basic_sphere<float> (48 B)");
+    const P probes[2] = { P(typename is_generic_primitive<P>::triangle_type()), P(typename is_generic_primitive<P>::sphere_type()) };
+    for (uint32_t k = 0; k < 2; ++k)
+    {
+        uint32_t type = 0;
+        std::memcpy(&type, reinterpret_cast<const unsigned char*>(&probes[k]) + VRH_GENERIC_TYPE_OFFSET, 4);
+        if (type != k + 1u) throw hip_error("hip_index_bvh: generic_primitive keeps no type index at byte 64", VRH_ERR_INVALID);
+    }
+}
+template <typename P>
+inline typename std::enable_if<!is_generic_primitive<P>::value>::type check_record_layout()
+{
+    static_assert(sizeof(P) == prim_bytes_of<P>(), "primitive layout must match basic_triangle<3,float> / basic_sphere<float>");
+}
+
 template <typename SP, typename = void> struct has_scissor : std::false_type {};
 template <typename SP> struct has_scissor<SP, decltype((void)std::declval<SP>().scissor_box)> : std::true_type {};
 
@@ -237,6 +274,9 @@ public:
         if (!scratch_->declined) return;
         const uint32_t depth = __atomic_exchange_n(scratch_->declined, 0u, __ATOMIC_ACQUIRE);
         if (depth == 0u) return;
+        if (depth == 0xFFFFFFFFu)      // hip_kernels.h USER_DECLINED_GENERIC
+            throw hip_error("hip_sched: user kernel: user kernels do not traverse generic-primitive scenes (VRH_PRIM_GENERIC80):"
+                            " its closest_hit / any_hit calls were not traversed", VRH_ERR_UNSUPPORTED);
         const std::string what = "hip_sched: user kernel: a BVH of depth " + std::to_string(depth) + " needs "
                                  + std::to_string(uint64_t(depth) + 1u) + " traversal stack entries, the launch gave "
                                  + std::to_string(scratch_->stack_entries)
@@ -358,8 +398,10 @@ class hip_index_bvh
 public:
     using primitive_type = Primitive;
     using bvh_ref = hip_bvh_ref_t<Primitive>;      // cuda_index_bvh<P>::bvh_ref (bvh.h:344)
-    static_assert(hip_detail::is_triangle<Primitive>::value || hip_detail::is_sphere<Primitive>::value,
-                  "hip_index_bvh supports basic_triangle<3,float> and basic_sphere<float>");
+    static_assert(hip_detail::is_triangle<Primitive>::value || hip_detail::is_sphere<Primitive>::value
+                      || hip_detail::is_generic_primitive<Primitive>::value,
+                  "hip_index_bvh supports basic_triangle<3,float>, basic_sphere<float> and generic_primitive of the two");
+    static_assert(sizeof(Primitive) == hip_detail::prim_bytes_of<Primitive>(), "primitive record size (64, 48 or 80 bytes)");
 
     // host_bvh: index_bvh<P> (nodes(), indices(), primitives()); face_normals: 16-B vec3 per
     // primitive (normals_per_face_binding, get_normal.h:26-37), needed by the AO kernel
@@ -369,12 +411,13 @@ public:
         : ctx_(std::move(ctx))
     {
         static_assert(sizeof(*host_bvh.nodes().data()) == 32, "bvh_node must be 32 bytes");
-        static_assert(sizeof(Primitive) == (hip_detail::is_sphere<Primitive>::value ? 48 : 64),
-                      "primitive layout must match basic_triangle<3,float> / basic_sphere<float>");
+        // (a generic_primitive list uploads its 80-byte records as they lie in memory; face_normals: one row per
+        // prim_id, read for triangles only)
+        hip_detail::check_record_layout<Primitive>();
         vrh_scene* s = nullptr;
         hip_detail::check(vrh_scene_upload(ctx_->get(), host_bvh.nodes().data(), uint32_t(host_bvh.nodes().size()),
                                            host_bvh.primitives().data(), uint32_t(host_bvh.primitives().size()),
-                                           hip_detail::is_sphere<Primitive>::value ? VRH_PRIM_SPHERE48 : VRH_PRIM_TRI64,
+                                           hip_detail::prim_kind_of<Primitive>(),
                                            host_bvh.indices().data(), uint32_t(host_bvh.indices().size()),
                                            face_normals, &s),
                           "vrh_scene_upload");
@@ -397,7 +440,7 @@ public:
         vrh_build_desc desc{ VRH_BUILD_LBVH, max_leaf };
         vrh_scene* s = nullptr;
         hip_detail::check(vrh_scene_build(ctx->get(), prims.data(), uint32_t(prims.size()),
-                                          hip_detail::is_sphere<Primitive>::value ? VRH_PRIM_SPHERE48 : VRH_PRIM_TRI64,
+                                          hip_detail::prim_kind_of<Primitive>(),
                                           rows.empty() ? nullptr : rows.data(), &desc, &s),
                           "vrh_scene_build");
         return hip_index_bvh(s, std::move(ctx));
@@ -422,6 +465,10 @@ public:
     // the device arrays, passed by value into user kernels (visionaray_hip/hip_kernels.h)
     hip_bvh_ref_t<Primitive> ref() const
     {
+        static_assert(!hip_detail::is_generic_primitive<Primitive>::value,
+                      "hip_index_bvh<generic_primitive<...>>::ref(): user kernels do not traverse generic primitives -- "
+                      "render them with the built-in kernels (make_hip_closest_hit_kernel, make_hip_ao_kernel, "
+                      "make_hip_simple_kernel, make_hip_whitted_kernel)");
         hip_bvh_ref_t<Primitive> r{};
         hip_detail::check(vrh_scene_get_view(handle(), 0, &r.view), "vrh_scene_get_view");
         hip_detail::note_ref_depth(r.view.max_depth);
@@ -1238,8 +1285,7 @@ unsigned hip_build_index_bvh(Primitive const* prims, size_t n, NodeVec& nodes, I
     nodes.resize(2 * n);
     indices.resize(n);
     uint32_t nn = 0, depth = 0;
-    hip_detail::check(vrh_build_bvh(prims, uint32_t(n),
-                                    hip_detail::is_sphere<Primitive>::value ? VRH_PRIM_SPHERE48 : VRH_PRIM_TRI64,
+    hip_detail::check(vrh_build_bvh(prims, uint32_t(n), hip_detail::prim_kind_of<Primitive>(),
                                     nodes.data(), &nn, indices.data(), &depth),
                       "vrh_build_bvh");
     nodes.resize(nn);

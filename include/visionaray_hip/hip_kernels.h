@@ -511,6 +511,18 @@ __device__ __attribute__((cold)) inline void user_walk_declined(uint32_t depth)
     uint32_t* word = reinterpret_cast<uint32_t*>(uintptr_t(s[0]) | (uintptr_t(s[1]) << 32));
     if (word) __hip_atomic_store(word, depth, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
+// A view of a generic-primitive scene (VRH_PRIM_GENERIC80: triangles and spheres in one list) is not walked by user
+// kernels -- their leaf code decides "triangle, else sphere" from the view's kind -- and takes the same route as a
+// BVH too deep: declined on the device with this code in the declined-walk word, VRH_ERR_UNSUPPORTED on the host.
+constexpr uint32_t USER_DECLINED_GENERIC = 0xFFFFFFFFu;
+__device__ inline bool user_view_refused(vrh_scene_view const& b, uint32_t entries)
+{
+    return b.max_depth >= entries || b.prim_kind > VRH_PRIM_SPHERE48;
+}
+__device__ inline uint32_t user_refusal_code(vrh_scene_view const& b)
+{
+    return b.prim_kind > VRH_PRIM_SPHERE48 ? USER_DECLINED_GENERIC : b.max_depth;
+}
 __device__ inline vrh::dev::lds_stack user_stack()
 {
     extern __shared__ uint32_t vrh_user_smem[];
@@ -924,7 +936,7 @@ __device__ inline bool walk_quads(vrh_scene_view const& b, vrh::dev::ray_t const
 template <bool ANY = false, typename Ray, typename CullT, typename Leaf>
 __device__ inline void walk(vrh_scene_view const& b, Ray const& ray, float max_t, CullT const& cull_t, Leaf&& leaf)
 {
-    if (__builtin_expect(b.max_depth >= user_stack_entries(), 0)) { user_walk_declined(b.max_depth); return; }
+    if (__builtin_expect(user_view_refused(b, user_stack_entries()), 0)) { user_walk_declined(user_refusal_code(b)); return; }
     const vrh::dev::ray_t r = dev_ray(ray);
     const bool fast = b.finite_bounds && vrh::dev::finite_ray(r);
     if constexpr (ANY && !VRH_USER_BINARY_ANYHIT)
@@ -1625,7 +1637,7 @@ VRH_FUNC inline auto intersect(
         (void)hip_detail::first_lane_ptr(view.pairs, same_bvh);
         if (same_bvh)
         {
-            if (__builtin_expect(view.max_depth >= VRH_USER_STACK, 0)) { hip_detail::user_walk_declined(view.max_depth); return result; }
+            if (__builtin_expect(hip_detail::user_view_refused(view, VRH_USER_STACK), 0)) { hip_detail::user_walk_declined(hip_detail::user_refusal_code(view)); return result; }
             const vrh::dev::ray_t r = hip_detail::dev_ray(ray);
             auto leaf2 = [&](vrh::dev::ray_t const& tr, float tmax, uint32_t i, uint32_t& flags, RT& rec) -> bool
             {
@@ -1650,7 +1662,7 @@ VRH_FUNC inline auto intersect(
                                && std::is_same<Intersector, default_intersector>::value && std::is_same<Cond, is_closer_t>::value;
     if constexpr (orderable)
     {
-        if (__builtin_expect(view.max_depth >= VRH_USER_STACK, 0)) { hip_detail::user_walk_declined(view.max_depth); return result; }
+        if (__builtin_expect(hip_detail::user_view_refused(view, VRH_USER_STACK), 0)) { hip_detail::user_walk_declined(hip_detail::user_refusal_code(view)); return result; }
         if (hip_detail::oca_wave_usable(view))
         {
             const vrh::dev::ray_t r = hip_detail::dev_ray(ray);
@@ -1757,7 +1769,7 @@ __device__ inline bvh_record traverse_bvh_direct(basic_ray<float> const& ray, vr
         (void)first_lane_ptr(b.pairs, same_bvh);
         if (same_bvh)
         {
-            if (__builtin_expect(b.max_depth >= VRH_USER_STACK, 0)) { user_walk_declined(b.max_depth); return result; }
+            if (__builtin_expect(user_view_refused(b, VRH_USER_STACK), 0)) { user_walk_declined(user_refusal_code(b)); return result; }
             const vrh::dev::ray_t r = dev_ray(ray);
             auto leaf2 = [&](vrh::dev::ray_t const& tr, float tmax, uint32_t i, uint32_t& flags, bvh_record& rec) -> bool
             {
@@ -1777,7 +1789,7 @@ __device__ inline bvh_record traverse_bvh_direct(basic_ray<float> const& ray, vr
     if constexpr (Any && VRH_USER_ANYHIT_ORDERED && std::is_same<Isect, default_intersector>::value)
     {
         // the ordered cooperative walk (walk_ordered): the reference's first hit, lanes sharing the work
-        if (__builtin_expect(b.max_depth >= VRH_USER_STACK, 0)) { user_walk_declined(b.max_depth); return result; }
+        if (__builtin_expect(user_view_refused(b, VRH_USER_STACK), 0)) { user_walk_declined(user_refusal_code(b)); return result; }
         if (oca_wave_usable(b))
         {
             const vrh::dev::ray_t r = dev_ray(ray);
@@ -2595,6 +2607,8 @@ __device__ inline vector<4, float> tex1D(hip_transfunc_ref const& tex, float coo
 template <typename Ref>
 inline Ref checked_ref(Ref r)
 {
+    if (r.view.prim_kind > VRH_PRIM_SPHERE48)
+        throw hip_error("hip_bvh_ref: user kernels do not traverse generic-primitive scenes (VRH_PRIM_GENERIC80)", VRH_ERR_UNSUPPORTED);
     if (r.view.max_depth >= VRH_USER_STACK)
         throw hip_error("hip_bvh_ref: BVH deeper than VRH_USER_STACK", VRH_ERR_UNSUPPORTED);
     hip_detail::note_ref_depth(r.view.max_depth);

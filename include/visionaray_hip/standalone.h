@@ -172,6 +172,31 @@ struct basic_sphere : primitive<P>
     VRH_FUNC basic_sphere(vector<3, T> const& c, T r) : center(c), radius(r) {}
 };
 
+// generic_primitive<basic_triangle<3, float>, basic_sphere<float>> (generic_primitive.h, variant.h): one list, and one
+// BVH, over triangles and spheres.  The reference's record: the alternative's bytes at 0, the variant's type index
+// at 64 (1 for the first alternative, 2 for the second), padding to 80, aligned to 16 -- VRH_PRIM_GENERIC80 takes it
+// verbatim.  The stand-in holds exactly these two alternatives.
+template <typename Tri, typename Sphere>
+struct generic_primitive
+{
+    static_assert(sizeof(Tri) == 64 && sizeof(Sphere) == 48, "generic_primitive<basic_triangle<3, float>, basic_sphere<float>>");
+    alignas(16) unsigned char storage[64];
+    unsigned type_index;
+    unsigned pad_[3];
+
+    generic_primitive() : storage{}, type_index(0), pad_{} {}
+    generic_primitive(Tri const& t) : storage{}, type_index(1), pad_{} { std::memcpy(storage, &t, sizeof(Tri)); }
+    generic_primitive(Sphere const& s) : storage{}, type_index(2), pad_{} { std::memcpy(storage, &s, sizeof(Sphere)); }
+    bool is_triangle() const { return type_index == 1; }
+    bool is_sphere() const { return type_index == 2; }
+    Tri triangle() const { Tri t; std::memcpy(&t, storage, sizeof(Tri)); return t; }
+    Sphere sphere() const { Sphere s; std::memcpy(&s, storage, sizeof(Sphere)); return s; }
+};
+using generic_triangle_sphere = generic_primitive<basic_triangle<3, float>, basic_sphere<float>>;
+static_assert(sizeof(generic_triangle_sphere) == 80 && alignof(generic_triangle_sphere) == 16
+                  && offsetof(generic_triangle_sphere, type_index) == VRH_GENERIC_TYPE_OFFSET,
+              "the generic primitive record: 80 bytes, the type index at 64");
+
 struct aabb
 {
     vec3 min, max;

@@ -64,8 +64,18 @@ enum vrh_status {
  * SURVEY.md Appendix C) */
 enum vrh_prim_kind {
     VRH_PRIM_TRI64 = 0,       /* basic_triangle<3,float>: geom_id@0 prim_id@4 v1@16 e1@32 e2@48 */
-    VRH_PRIM_SPHERE48 = 1     /* basic_sphere<float>:     geom_id@0 prim_id@4 center@16 radius@32 */
+    VRH_PRIM_SPHERE48 = 1,    /* basic_sphere<float>:     geom_id@0 prim_id@4 center@16 radius@32 */
+    /* generic_primitive<basic_triangle<3,float>, basic_sphere<float>>: the alternative's bytes (one of
+     * the two layouts above) at 0, u32 type index at 64 (1 triangle, 2 sphere; anything else is
+     * VRH_ERR_INVALID), padding to 80.  One BVH over both kinds: vrh_build_bvh, vrh_scene_upload and
+     * vrh_render with VRH_KERNEL_PRIMARY / AO / SIMPLE / WHITTED, one frame per launch, per-face normals
+     * (read for triangles only; a sphere's normal is (isect_pos - center) / radius).  Every other use of
+     * such a scene returns VRH_ERR_UNSUPPORTED. */
+    VRH_PRIM_GENERIC80 = 2
 };
+#define VRH_GENERIC_TYPE_OFFSET 64u
+#define VRH_GENERIC_TYPE_TRI 1u
+#define VRH_GENERIC_TYPE_SPHERE 2u
 
 /* built-in kernels (a C ABI cannot carry an arbitrary C++ lambda; SURVEY.md §7 hard part 6) */
 enum vrh_kernel_kind {

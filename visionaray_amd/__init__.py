@@ -7,11 +7,11 @@ multi-GPU render groups (render_group, render_sharded: image-tile shards gathere
 """
 from . import _capi
 from ._capi import VrhError
-from .api import (BVH_NODE_DTYPE, DEGREES_TO_RADIANS, GROUP_ID_BYTES, MATERIAL_DTYPE, MATERIAL_EMISSIVE, MATERIAL_MATTE,
+from .api import (BVH_NODE_DTYPE, DEGREES_TO_RADIANS, GENERIC_DTYPE, GENERIC_TYPE_SPHERE, GENERIC_TYPE_TRIANGLE, GROUP_ID_BYTES, MATERIAL_DTYPE, MATERIAL_EMISSIVE, MATERIAL_MATTE,
                   MATERIAL_MIRROR, MATERIAL_PLASTIC, PLASTIC_DTYPE, POINT_LIGHT_DTYPE,
                   SPHERE_DTYPE, TRIANGLE_DTYPE, Context, ao_kernel, broadcast_scene, build_index_bvh, camera, closest_hit_kernel,
                   device_count, emissive, face_normals, generic_materials, generic_shading, hip_buffer_rt, hip_index_bvh, hip_sched,
-                  hit_mask, index_bvh, load_obj, load_pnm, make_sched_params, make_spheres, make_triangles, matrix_inverse, matte, mirror, model,
+                  hit_mask, index_bvh, load_obj, load_pnm, make_generic, make_sched_params, make_spheres, make_triangles, matrix_inverse, matte, mirror, model,
                   multi_hit_kernel, normals_per_face_binding, normals_per_vertex_binding, pathtracing_kernel, pixel_sampler,
                   plastic,
                   point_light, render, render_batch, render_group, render_sampled, render_sharded, render_view, sah_cost, shading,
@@ -19,11 +19,11 @@ from .api import (BVH_NODE_DTYPE, DEGREES_TO_RADIANS, GROUP_ID_BYTES, MATERIAL_D
                   volume_desc, volume_kernel, volume_kernel_desc, volume_render_host, whitted_kernel, with_hit_mask)
 
 __all__ = [
-    "BVH_NODE_DTYPE", "DEGREES_TO_RADIANS", "GROUP_ID_BYTES", "MATERIAL_DTYPE", "MATERIAL_EMISSIVE", "MATERIAL_MATTE",
+    "BVH_NODE_DTYPE", "DEGREES_TO_RADIANS", "GENERIC_DTYPE", "GENERIC_TYPE_SPHERE", "GENERIC_TYPE_TRIANGLE", "GROUP_ID_BYTES", "MATERIAL_DTYPE", "MATERIAL_EMISSIVE", "MATERIAL_MATTE",
     "MATERIAL_MIRROR", "MATERIAL_PLASTIC", "PLASTIC_DTYPE", "POINT_LIGHT_DTYPE", "SPHERE_DTYPE",
     "TRIANGLE_DTYPE", "Context", "VrhError", "_capi", "ao_kernel", "broadcast_scene", "build_index_bvh", "camera", "closest_hit_kernel",
     "device_count", "emissive", "face_normals", "generic_materials", "generic_shading", "hip_buffer_rt", "hip_index_bvh", "hip_sched",
-    "hit_mask", "index_bvh", "load_obj", "load_pnm", "make_sched_params", "make_spheres", "make_triangles", "matrix_inverse", "matte", "mirror", "model",
+    "hit_mask", "index_bvh", "load_obj", "load_pnm", "make_generic", "make_sched_params", "make_spheres", "make_triangles", "matrix_inverse", "matte", "mirror", "model",
     "multi_hit_kernel", "normals_per_face_binding", "normals_per_vertex_binding", "pathtracing_kernel", "pixel_sampler",
     "plastic",
     "point_light", "render", "render_batch", "render_group", "render_sampled", "render_sharded", "render_view", "sah_cost",

@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("VRH_LIB") or os.path.join(_HERE, "_lib", "libvrh.so")
 # enums (vrh.h)
 VRH_OK, VRH_ERR_INVALID, VRH_ERR_HIP, VRH_ERR_OOM, VRH_ERR_UNSUPPORTED, VRH_ERR_NO_DEVICE, VRH_ERR_TIMEOUT = range(7)
 VRH_GROUP_TIMEOUT_MS = 120000
-VRH_PRIM_TRI64, VRH_PRIM_SPHERE48 = 0, 1
+VRH_PRIM_TRI64, VRH_PRIM_SPHERE48, VRH_PRIM_GENERIC80 = 0, 1, 2
 VRH_KERNEL_PRIMARY, VRH_KERNEL_AO, VRH_KERNEL_SIMPLE, VRH_KERNEL_MULTI_HIT, VRH_KERNEL_WHITTED = 0, 1, 2, 3, 4
 VRH_KERNEL_PATHTRACING = 5
 VRH_MAX_HITS = 16

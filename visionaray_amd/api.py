@@ -26,6 +26,10 @@ TRIANGLE_DTYPE = np.dtype([("geom_id", "<u4"), ("prim_id", "<u4"), ("pad", "<u4"
                            ("v1", "<f4", 4), ("e1", "<f4", 4), ("e2", "<f4", 4)])
 SPHERE_DTYPE = np.dtype([("geom_id", "<u4"), ("prim_id", "<u4"), ("pad", "<u4", 2),
                          ("center", "<f4", 4), ("radius", "<f4"), ("pad2", "<f4", 3)])
+# generic_primitive<basic_triangle<3,float>, basic_sphere<float>>: the alternative's bytes, the variant's type
+# index (1 triangle, 2 sphere) at 64, padding to 80
+GENERIC_DTYPE = np.dtype([("data", "u1", 64), ("type", "<u4"), ("pad", "<u4", 3)])
+GENERIC_TYPE_TRIANGLE, GENERIC_TYPE_SPHERE = 1, 2
 BVH_NODE_DTYPE = np.dtype([("bbox_min", "<f4", 3), ("first", "<u4"), ("bbox_max", "<f4", 3), ("num_prims", "<u4")])
 
 
@@ -38,7 +42,9 @@ def _kind_of(prims):
         return capi.VRH_PRIM_TRI64
     if prims.dtype == SPHERE_DTYPE:
         return capi.VRH_PRIM_SPHERE48
-    raise TypeError(f"unsupported primitive dtype {prims.dtype}; use TRIANGLE_DTYPE or SPHERE_DTYPE")
+    if prims.dtype == GENERIC_DTYPE:
+        return capi.VRH_PRIM_GENERIC80
+    raise TypeError(f"unsupported primitive dtype {prims.dtype}; use TRIANGLE_DTYPE, SPHERE_DTYPE or GENERIC_DTYPE")
 
 
 # ---- primitives -------------------------------------------------------------------------------
@@ -64,6 +70,29 @@ def make_spheres(center, radius, prim_id=None, geom_id=None):
     s["prim_id"] = np.arange(n, dtype=np.uint32) if prim_id is None else prim_id
     s["geom_id"] = 0 if geom_id is None else geom_id
     return s
+
+
+def make_generic(triangles=None, spheres=None, order=None):
+    """generic_primitive<basic_triangle<3,float>, basic_sphere<float>> array (GENERIC_DTYPE) holding the given
+    TRIANGLE_DTYPE and SPHERE_DTYPE records as they are (prim_id / geom_id included: give every primitive of the
+    list its own prim_id).  order: for each output slot 0 (the next triangle) or 1 (the next sphere), to
+    interleave the two kinds; None puts the triangles first."""
+    tris = np.zeros(0, TRIANGLE_DTYPE) if triangles is None else np.ascontiguousarray(triangles)
+    sphs = np.zeros(0, SPHERE_DTYPE) if spheres is None else np.ascontiguousarray(spheres)
+    if tris.dtype != TRIANGLE_DTYPE or sphs.dtype != SPHERE_DTYPE:
+        raise TypeError("make_generic(triangles: TRIANGLE_DTYPE, spheres: SPHERE_DTYPE)")
+    n = len(tris) + len(sphs)
+    if order is None:
+        order = np.concatenate([np.zeros(len(tris), np.uint8), np.ones(len(sphs), np.uint8)])
+    order = np.asarray(order)
+    if order.shape != (n,) or int((order == 0).sum()) != len(tris) or int((order == 1).sum()) != len(sphs):
+        raise ValueError("make_generic: order must hold one 0 per triangle and one 1 per sphere")
+    g = np.zeros(n, GENERIC_DTYPE)
+    is_s = order == 1
+    g["data"][~is_s] = tris.view(np.uint8).reshape(len(tris), 64)
+    g["data"][is_s, :48] = sphs.view(np.uint8).reshape(len(sphs), 48)
+    g["type"] = np.where(is_s, GENERIC_TYPE_SPHERE, GENERIC_TYPE_TRIANGLE)
+    return g
 
 
 def face_normals(tris):
@@ -282,7 +311,7 @@ class hip_index_bvh:
         self = cls.__new__(cls)
         self.ctx = ctx
         prims = np.ascontiguousarray(prims)
-        kind = capi.VRH_PRIM_TRI64 if prims.dtype == TRIANGLE_DTYPE else capi.VRH_PRIM_SPHERE48
+        kind = _kind_of(prims)
         nrm = None if normals is None else np.ascontiguousarray(normals, np.float32)
         h = C.c_void_p()
         desc = capi.vrh_build_desc(capi.VRH_BUILD_LBVH, max_leaf)

@@ -294,24 +294,17 @@ int build_impl(size_t n, GetBox get_box, node32* nodes_out, uint32_t* num_nodes_
 int build_bvh(const void* prims, uint32_t n, uint32_t kind, node32* nodes_out, uint32_t* num_nodes_out,
               uint32_t* indices_out, uint32_t* max_depth_out)
 {
-    if (kind == VRH_PRIM_TRI64)
-    {
-        auto tris = static_cast<const tri64*>(prims);
-        return build_impl(n, [&](size_t i) {
-            const tri64& t = tris[i];
-            bounds3 b; b.reset();
-            float p[3];
-            b.grow(t.v1);
-            for (int a = 0; a < 3; ++a) p[a] = t.v1[a] + t.e1[a];
-            b.grow(p);
-            for (int a = 0; a < 3; ++a) p[a] = t.v1[a] + t.e2[a];
-            b.grow(p);
-            return b;
-        }, nodes_out, num_nodes_out, indices_out, max_depth_out);
-    }
-    auto sph = static_cast<const sphere48*>(prims);
-    return build_impl(n, [&](size_t i) {
-        const sphere48& s = sph[i];
+    auto tri_box = [](const tri64& t) {
+        bounds3 b; b.reset();
+        float p[3];
+        b.grow(t.v1);
+        for (int a = 0; a < 3; ++a) p[a] = t.v1[a] + t.e1[a];
+        b.grow(p);
+        for (int a = 0; a < 3; ++a) p[a] = t.v1[a] + t.e2[a];
+        b.grow(p);
+        return b;
+    };
+    auto sphere_box = [](const sphere48& s) {             // sphere.inl:29-38
         bounds3 b; b.reset();
         float p[3];
         for (int a = 0; a < 3; ++a) p[a] = s.center[a] - s.radius;
@@ -319,7 +312,23 @@ int build_bvh(const void* prims, uint32_t n, uint32_t kind, node32* nodes_out, u
         for (int a = 0; a < 3; ++a) p[a] = s.center[a] + s.radius;
         b.grow(p);
         return b;
-    }, nodes_out, num_nodes_out, indices_out, max_depth_out);
+    };
+    if (kind == VRH_PRIM_TRI64)
+    {
+        auto tris = static_cast<const tri64*>(prims);
+        return build_impl(n, [&](size_t i) { return tri_box(tris[i]); }, nodes_out, num_nodes_out, indices_out, max_depth_out);
+    }
+    if (kind == VRH_PRIM_GENERIC80)
+    {
+        // a generic primitive's bounds are its alternative's (the variant visitor of get_bounds); the type
+        // indices were checked by the caller
+        auto gen = static_cast<const generic80*>(prims);
+        return build_impl(n, [&](size_t i) {
+            return gen[i].type == VRH_GENERIC_TYPE_SPHERE ? sphere_box(gen[i].sphere) : tri_box(gen[i].tri);
+        }, nodes_out, num_nodes_out, indices_out, max_depth_out);
+    }
+    auto sph = static_cast<const sphere48*>(prims);
+    return build_impl(n, [&](size_t i) { return sphere_box(sph[i]); }, nodes_out, num_nodes_out, indices_out, max_depth_out);
 }
 
 } // namespace vrh

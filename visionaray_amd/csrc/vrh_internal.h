@@ -5,6 +5,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -31,7 +32,50 @@ struct sphere48                                   // basic_sphere<float>
 };
 static_assert(sizeof(node32) == 32, "node layout");
 static_assert(sizeof(tri64) == 64, "triangle layout");
+struct generic80                                  // generic_primitive<basic_triangle<3,float>, basic_sphere<float>>
+{
+    union { tri64 tri; sphere48 sphere; };
+    uint32_t type;                                // 1 triangle, 2 sphere (the variant's type index)
+    uint32_t pad[3];
+};
 static_assert(sizeof(sphere48) == 48, "sphere layout");
+static_assert(sizeof(generic80) == 80 && offsetof(generic80, type) == VRH_GENERIC_TYPE_OFFSET, "generic primitive layout");
+
+// bytes of one host record of a primitive kind (0: unknown kind)
+constexpr uint32_t prim_record_bytes(uint32_t kind)
+{
+    return kind == VRH_PRIM_TRI64 ? 64u : kind == VRH_PRIM_SPHERE48 ? 48u : kind == VRH_PRIM_GENERIC80 ? 80u : 0u;
+}
+
+// Device flags word of a leaf-ordered primitive (vrh_device.h): bit 0 END_BIT, bit 1 the record is a sphere
+// (generic scenes only).
+constexpr uint32_t PRIM_FLAG_END = 1u, PRIM_FLAG_SPHERE = 2u;
+
+// The device leaf record of one generic primitive, three 16-byte words (the triangle format; a sphere keeps
+// centre and radius in the first word, both keep prim_id, geom_id and flags in the third).  Host-only and
+// header-only so that a stand-alone program can run it under a sanitizer.  False: the type index is neither
+// 1 nor 2.
+inline bool generic_leaf_record(const generic80& g, bool end, uint32_t out[12])
+{
+    for (int k = 0; k < 12; ++k) out[k] = 0u;
+    if (g.type == VRH_GENERIC_TYPE_TRI)
+    {
+        const tri64& t = g.tri;
+        const float w[9] = { t.v1[0], t.v1[1], t.v1[2], t.e1[0], t.e1[1], t.e1[2], t.e2[0], t.e2[1], t.e2[2] };
+        std::memcpy(out, w, sizeof w);
+        out[9] = t.prim_id; out[10] = t.geom_id; out[11] = end ? PRIM_FLAG_END : 0u;
+        return true;
+    }
+    if (g.type == VRH_GENERIC_TYPE_SPHERE)
+    {
+        const sphere48& s = g.sphere;
+        const float w[4] = { s.center[0], s.center[1], s.center[2], s.radius };
+        std::memcpy(out, w, sizeof w);
+        out[9] = s.prim_id; out[10] = s.geom_id; out[11] = PRIM_FLAG_SPHERE | (end ? PRIM_FLAG_END : 0u);
+        return true;
+    }
+    return false;
+}
 
 void set_error(const std::string& msg);
 

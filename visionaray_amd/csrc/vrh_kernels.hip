@@ -371,7 +371,10 @@ __device__ __forceinline__ uint32_t lane_rank(uint64_t mask)
 
 // AO ray s of hit slot `slot` whose pixel has global index p in frame f of the launch
 // (ao/main.cpp:216-238 with the Appendix-A sampler, offset by the frame number)
-template <bool COUNT, bool SHORT>
+// GEN: a generic-primitive scene -- the slot's fourth word is the hit's leaf-order index, whose record says
+// whether the normal is normals[prim_id] (triangle) or (isect_pos - center) / radius (sphere), as get_surface
+// finds it (get_normal.h:135-138); a sphere's entry of the normals is not read
+template <bool COUNT, bool SHORT, bool GEN = false>
 __device__ __forceinline__ ray_t ao_ray(const render_params& P, const float* recs, uint32_t slot, uint32_t s,
                                         uint32_t p, uint32_t f, test_counts& cnt)
 {
@@ -383,9 +386,25 @@ __device__ __forceinline__ ray_t ao_ray(const render_params& P, const float* rec
     if constexpr (SHORT) rec = *reinterpret_cast<const float4*>(sr);
     else rec = make_float4(sr[0], sr[1], sr[2], sr[3]);
     f3 pos = mk3(rec.x, rec.y, rec.z);
-    const float4* np = P.normals + __float_as_uint(rec.w);
-    const float4 nn = *np;                                             // get_normal.h:26-37
-    if (COUNT) count_vmem(cnt, np, 1u, VMEM_NORMAL);
+    float4 nn;
+    if constexpr (GEN)
+    {
+        const float4* q = P.prims + 3u * __float_as_uint(rec.w);
+        const float4 qc = q[2];
+        if (__float_as_uint(qc.w) & SPHERE_BIT)
+        {
+            const float4 qa = q[0];
+            nn = make_float4((pos.x - qa.x) / qa.w, (pos.y - qa.y) / qa.w, (pos.z - qa.z) / qa.w, 0.0f);
+        }
+        else
+            nn = P.normals[__float_as_uint(qc.y)];                         // get_normal.h:26-37
+    }
+    else
+    {
+        const float4* np = P.normals + __float_as_uint(rec.w);
+        nn = *np;                                                      // get_normal.h:26-37
+        if (COUNT) count_vmem(cnt, np, 1u, VMEM_NORMAL);
+    }
     const uint32_t salt = frame_salt(P.frame_num + f);
     float sx = 0.0f, sy = 0.0f;
     if (SHORT) ao_disk_sample(p, s, salt, sx, sy);
@@ -633,10 +652,17 @@ __device__ __forceinline__ uint32_t kernarg_stack_cap()
 // SPILL: the traversal stack may continue in the global overflow block (stack_t<true>).
 // TEX: the shading samples its diffuse maps at every surface it sets up (vrh_shading_set_textures; vrh_shade.h
 // surface_tex): EPI 1, 3, 4, 5.  The untextured instances are the same code as before the argument existed.
+// GEN: the scene holds generic primitives (VRH_PRIM_GENERIC80: triangles and spheres in one BVH; KIND is 0, the
+// leaf loop is KIND_GENERIC's): EPI 0 with and without AO, 1 and 3, the one-frame step loop, the whole stack in
+// LDS (vrh_launch.h generic_instance_exists).  Every other instance is the code it was before the argument existed.
 template <int KIND, bool AO, bool COUNT, int OCC, int EPI = 0, bool LIST = false, bool BATCH = false, bool SPILL = false,
-          bool SAMPLED = false, bool SHARE = false, bool TEX = false>
+          bool SAMPLED = false, bool SHARE = false, bool TEX = false, bool GEN = false>
 __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params P)
 {
+    static_assert(!GEN || (KIND == KIND_TRI && !COUNT && !LIST && !BATCH && !SPILL && !SAMPLED && !SHARE && !TEX
+                           && (EPI == 0 || ((EPI == 1 || EPI == 3) && !AO))),
+                  "generic primitives: primary, AO, simple and whitted on the one-frame step loop");
+    constexpr int TK = GEN ? KIND_GENERIC : KIND;      // the leaf loop's primitive kind
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
     const uint32_t tid = threadIdx.x;
     const uint32_t lane = tid & 63u;
@@ -748,8 +774,8 @@ __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params 
             if (mode != IDLE)
             {
                 int rc = (P.fast_ok && __ballot(!finite) == 0ull)
-                    ? ray_step<KIND, COUNT, true, UV, ML>(P.pairs, P.prims, P.quads, P.root, quad, r, mt, an, st, best_t, best_prim, cnt, steps, P.step_limit, resume, P.descent_cap, P.step_flags, &hx, &mh, hm)
-                    : ray_step<KIND, COUNT, false, UV, ML>(P.pairs, P.prims, P.quads, P.root, quad, r, mt, an, st, best_t, best_prim, cnt, steps, P.step_limit, resume, P.descent_cap, P.step_flags, &hx, &mh, hm);
+                    ? ray_step<TK, COUNT, true, UV, ML>(P.pairs, P.prims, P.quads, P.root, quad, r, mt, an, st, best_t, best_prim, cnt, steps, P.step_limit, resume, P.descent_cap, P.step_flags, &hx, &mh, hm)
+                    : ray_step<TK, COUNT, false, UV, ML>(P.pairs, P.prims, P.quads, P.root, quad, r, mt, an, st, best_t, best_prim, cnt, steps, P.step_limit, resume, P.descent_cap, P.step_flags, &hx, &mh, hm);
                 if constexpr (LIST)
                     if (rc != 0) rc = list_next(P, false, bk, res_t, res_prim, best_t, best_prim, st, resume);
                 if constexpr (EPI == 3)
@@ -780,6 +806,7 @@ __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params 
                                 {
                                     w.depth += 1u;
                                     if constexpr (TEX) whitted_surface<true>(P.shade, P.prims, P.normals, w, r, best_t, best_prim, hx, &wtex);
+                                    else if constexpr (GEN) whitted_surface<false, true>(P.shade, P.prims, P.normals, w, r, best_t, best_prim, hx);
                                     else whitted_surface(P.shade, P.prims, P.normals, w, r, best_t, best_prim, hx);
                                 }
                                 else
@@ -789,7 +816,7 @@ __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params 
                         else
                         {
                             if constexpr (TEX) whitted_light_done<true>(P.shade, w, rc > 0, wtex);
-                            else whitted_light_done(P.shade, w, rc > 0);
+                            else whitted_light_done<false, GEN>(P.shade, w, rc > 0);
                         }
                         if (mode != IDLE && !done)
                         {
@@ -908,7 +935,7 @@ __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params 
                     hits_total += hit ? 1 : 0;
                     float4 c = hit ? make_float4(1.0f, 1.0f, 1.0f, 1.0f) : make_float4(P.bg[0], P.bg[1], P.bg[2], P.bg[3]);
                     if constexpr (EPI == 1)
-                        if (hit) c = shade_simple<TEX>(P.shade, P.prims, P.normals, r, best_t, best_prim, hx);
+                        if (hit) c = shade_simple<TEX, GEN>(P.shade, P.prims, P.normals, r, best_t, best_prim, hx);
                     if constexpr (EPI == 2)
                         c = shade_multi(P.shade, P.prims, P.normals, r, mh);
                     if (P.color) put_color<SAMPLED>(P, out_o, c);
@@ -965,6 +992,8 @@ __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params 
         // own, which the 6-wave instances spilled
         // owner wave << 12 (the wave whose tile the ray belongs to: this one unless it helps a sibling)
         uint32_t tag = 0;
+        [[maybe_unused]] hit_extra ghx = { 0.0f, 0.0f, 0u };     // GEN: the closest hit's leaf-order index (its record
+                                                                  // says whether the AO normal is a sphere's)
         constexpr bool SHORT_HANDOUT = !(SHARE || SAMPLED);       // hand-out path of this instance (ao_ray)
         // AO ray `cand` (slot-major: slot cand / S, sample cand % S) of the tile `tile` whose hit records,
         // slot pixels and cut are recs_ / spx / cut_, cutn (this wave's, or a sibling's it helps)
@@ -974,7 +1003,7 @@ __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params 
             const uint32_t slot = (cand * P.samples_recip) >> 20, smp = cand - slot * S;
             uint32_t x, y, orow, fr;
             tile_pixel(P, tile, spx[par * 64u + slot], x, y, orow, fr);
-            r = ao_ray<COUNT, SHORT_HANDOUT>(P, recs_, slot, smp, y * P.width + x, fr, cnt);
+            r = ao_ray<COUNT, SHORT_HANDOUT, GEN>(P, recs_, slot, smp, y * P.width + x, fr, cnt);
             best_t = FMAX; best_prim = 0; steps = 0; max_t = P.radius; any = true;
             bk = 0; res_t = FMAX; res_prim = 0;
             const bool fin = finite_ray(r);
@@ -1208,8 +1237,8 @@ __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params 
                 // (the same value init() formed; not in the tail-sharing instances, which it costs VGPR spills)
                 if constexpr (SPILL && !COUNT && !LIST && !SHARE && KERNARG_STACK_CAP) st.cap_off = kernarg_stack_cap() * block;
                 rc = (P.fast_ok && __ballot((tag & TAG_NONFINITE) != 0u) == 0ull)
-                    ? ray_step<KIND, COUNT, true, false, void, false, !LIST>(P.pairs, P.prims, LIST ? P.quads : P.aoquads, 0u, quad, r, mt, any, st, best_t, best_prim, cnt, steps, P.step_limit, resume, P.descent_cap, P.step_flags, nullptr, static_cast<const void*>(nullptr), hm, P.leaf_boxes)
-                    : ray_step<KIND, COUNT, false, false, void, false, !LIST>(P.pairs, P.prims, LIST ? P.quads : P.aoquads, 0u, quad, r, mt, any, st, best_t, best_prim, cnt, steps, P.step_limit, resume, P.descent_cap, P.step_flags, nullptr, static_cast<const void*>(nullptr), hm, P.leaf_boxes);
+                    ? ray_step<TK, COUNT, true, GEN, void, false, !LIST>(P.pairs, P.prims, LIST ? P.quads : P.aoquads, 0u, quad, r, mt, any, st, best_t, best_prim, cnt, steps, P.step_limit, resume, P.descent_cap, P.step_flags, GEN ? &ghx : nullptr, static_cast<const void*>(nullptr), hm, P.leaf_boxes)
+                    : ray_step<TK, COUNT, false, GEN, void, false, !LIST>(P.pairs, P.prims, LIST ? P.quads : P.aoquads, 0u, quad, r, mt, any, st, best_t, best_prim, cnt, steps, P.step_limit, resume, P.descent_cap, P.step_flags, GEN ? &ghx : nullptr, static_cast<const void*>(nullptr), hm, P.leaf_boxes);
             }
             if constexpr (LIST)
                 if (busy && rc < 0) rc = list_next(P, any, bk, res_t, res_prim, best_t, best_prim, st, resume);
@@ -1254,7 +1283,7 @@ __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params 
                         const f3 pos = r.ori + r.dir * best_t;                   // ao/main.cpp:202
                         float* rec = recs + slot * AO_REC_WORDS;
                         rec[0] = pos.x; rec[1] = pos.y; rec[2] = pos.z;
-                        rec[3] = __uint_as_float(best_prim);
+                        rec[3] = __uint_as_float(GEN ? ghx.li : best_prim);
                         masks[parC * 64u + slot] = 0u;
                         slot_px[parC * 64u + slot] = (uint8_t)(tag & 63u);
                     }
@@ -1306,28 +1335,31 @@ __global__ void pack_code_kernel(const uint32_t* __restrict__ pid, const uint8_t
 using kernel_fn = void (*)(render_params);
 
 // the instance of key_at(I), named here and nowhere else: null where instance_exists says there is none
-// (TEX: the textured instance of the key, where textured_instance_exists says there is one)
-template <size_t I, bool TEX>
+// (TEX: the textured instance of the key, where textured_instance_exists says there is one;
+// GEN: the generic-primitive instance of the key, where generic_instance_exists says there is one)
+template <size_t I, bool TEX, bool GEN>
 static kernel_fn instance_at()
 {
     constexpr instance_key k = key_at(I);
-    if constexpr (TEX ? textured_instance_exists(k) : instance_exists(k))
-        return dev::render_unified_kernel<k.kind, k.ao, k.count, k.occ, int(k.epi), k.list, k.batch, k.spill, k.sampled, k.share, TEX>;
+    static_assert(!(TEX && GEN), "no textured generic-primitive instances");
+    if constexpr (GEN ? generic_instance_exists(k) : TEX ? textured_instance_exists(k) : instance_exists(k))
+        return dev::render_unified_kernel<k.kind, k.ao, k.count, k.occ, int(k.epi), k.list, k.batch, k.spill, k.sampled, k.share, TEX, GEN>;
     else
         return nullptr;
 }
 
-template <bool TEX, size_t... I>
+template <bool TEX, bool GEN, size_t... I>
 static kernel_fn find_instance(size_t i, std::index_sequence<I...>)
 {
-    static const kernel_fn table[NUM_KEYS + 1] = { instance_at<I, TEX>()..., nullptr };
+    static const kernel_fn table[NUM_KEYS + 1] = { instance_at<I, TEX, GEN>()..., nullptr };
     return table[i];
 }
 
 static kernel_fn select_variant(const launch_config& c)
 {
-    return c.textured ? find_instance<true>(key_index(c), std::make_index_sequence<NUM_KEYS>{})
-                      : find_instance<false>(key_index(c), std::make_index_sequence<NUM_KEYS>{});
+    if (c.generic) return c.textured ? nullptr : find_instance<false, true>(key_index(c), std::make_index_sequence<NUM_KEYS>{});
+    return c.textured ? find_instance<true, false>(key_index(c), std::make_index_sequence<NUM_KEYS>{})
+                      : find_instance<false, false>(key_index(c), std::make_index_sequence<NUM_KEYS>{});
 }
 
 size_t render_lds_bytes(const launch_config& c)

@@ -88,6 +88,21 @@ constexpr bool textured_instance_exists(const instance_key& k)
     return (k.epi == EPI_SIMPLE || k.epi == EPI_WHITTED || k.epi == EPI_PATH || k.epi == EPI_PATH_GENERIC) && k.occ == 1;
 }
 
+// "Generic" is a third axis of the same form (render_unified_kernel's defaulted GEN argument): the instances whose
+// leaf loop walks generic primitives (VRH_PRIM_GENERIC80, triangles and spheres in one BVH).  The key's kind stays
+// 0 -- the records are the triangle's three words -- so the key domain, and every instance outside this axis, is
+// what it was.  The set: primary visibility, AO, simple and whitted on the one-frame step loop with the whole
+// stack in LDS, uncounted, one register budget each -- primary 6 waves / SIMD, AO and whitted 5, simple uncapped
+// (DESIGN.md section 3 has their resource usage).
+constexpr bool generic_instance_exists(const instance_key& k)
+{
+    if (!instance_exists(k) || k.kind != 0 || k.count || k.list || k.batch || k.spill || k.sampled || k.share) return false;
+    if (k.epi == EPI_PLAIN) return k.occ == (k.ao ? 5 : 6);
+    if (k.epi == EPI_SIMPLE) return k.occ == 1;
+    if (k.epi == EPI_WHITTED) return k.occ == 5;
+    return false;
+}
+
 // the key domain as a mixed-radix index (vrh_kernels.hip builds its table of instances over it)
 constexpr int KEY_OCCS[4] = { 1, 5, 6, 8 };
 constexpr size_t NUM_KEYS = 2 * 2 * 2 * 4 * 6 * 32;
@@ -117,6 +132,7 @@ struct launch_config : instance_key
     int stack_cap;     // LDS stack entries per lane
     int max_hits;      // MULTI_HIT: N (LDS hit lists)
     bool textured;     // the TEX instance of the key (textured_instance_exists)
+    bool generic = false;   // the GEN instance of the key (generic_instance_exists)
 };
 
 // dynamic LDS of a launch; `ao_wave_words` (the per-wave AO area) and `whitted_lane_words` (the
@@ -152,6 +168,7 @@ struct launch_inputs
     bool finite_bounds = true, has_quads = false, root_is_pair0 = true;
     bool radius_finite = true;              // AO: the radius is <= FLT_MAX (the 4-wide step's test relies on it)
     tuning_options opt;
+    bool generic = false;                   // the scene holds generic primitives (VRH_PRIM_GENERIC80)
 };
 
 // the two questions the plan asks the device side
@@ -203,8 +220,46 @@ constexpr int textured_family_occ(instance_key k, int want)
     return below ? below : least;
 }
 
+// the same among the generic-primitive instances
+constexpr int generic_family_occ(instance_key k, int want)
+{
+    int below = 0, least = 0;
+    for (int i = 3; i >= 0; --i)
+    {
+        k.occ = KEY_OCCS[i];
+        if (!generic_instance_exists(k)) continue;
+        least = k.occ;
+        if (below == 0 && k.occ <= want) below = k.occ;
+    }
+    return below ? below : least;
+}
+
+// A generic-primitive scene: what the launch asks for beyond the GEN instances is refused here, by name, before
+// anything is planned ("" where nothing is).
+inline std::string generic_refusal(const launch_inputs& in)
+{
+    const char* what = in.num_roots > 1 ? "BVH lists"
+                     : in.sampler_pass ? "pixel-sampler passes"
+                     : in.num_frames > 1 ? "frames in flight (vrh_render_batch)"
+                     : in.count_tests ? "test counting"
+                     : in.hit_mask ? "hit masks"
+                     : in.textured ? "textures"
+                     : in.kernel == VRH_KERNEL_MULTI_HIT ? "multi_hit"
+                     : in.kernel == VRH_KERNEL_PATHTRACING ? "the path tracer"
+                     : in.generic_shading ? "generic materials"
+                     : nullptr;
+    return what ? std::string("vrh_render: generic-primitive scenes do not support ") + what
+                    + " (primary, AO, simple and whitted, one frame per launch, one BVH)"
+                : std::string();
+}
+
 inline int plan_launch(const launch_inputs& in, const launch_device& dev, launch_plan& out, std::string& err)
 {
+    if (in.generic)
+    {
+        err = generic_refusal(in);
+        if (!err.empty()) return VRH_ERR_UNSUPPORTED;
+    }
     const tuning_options& opt = in.opt;
     const bool ao = in.kernel == VRH_KERNEL_AO;
     const bool multi = in.kernel == VRH_KERNEL_MULTI_HIT;
@@ -220,7 +275,8 @@ inline int plan_launch(const launch_inputs& in, const launch_device& dev, launch
     const uint32_t cap = opt.stack ? uint32_t(opt.stack) : total;
     if (cap < 1u) { err = "vrh_render: stack capacity option must be >= 1"; return VRH_ERR_INVALID; }
     launch_config lc{};
-    lc.kind = in.prim_kind == VRH_PRIM_TRI64 ? 0 : 1;
+    lc.kind = (in.generic || in.prim_kind == VRH_PRIM_TRI64) ? 0 : 1;
+    lc.generic = in.generic;
     lc.ao = ao;
     lc.count = in.count_tests;
     lc.stack_cap = int(cap);
@@ -278,10 +334,16 @@ inline int plan_launch(const launch_inputs& in, const launch_device& dev, launch
             return VRH_ERR_UNSUPPORTED;
         }
     }
+    if (in.generic)
+    {
+        // a generic-primitive scene runs the GEN instance of its key, at the one register budget it has
+        lc.occ = generic_family_occ(lc, opt.occ ? opt.occ : occ_default);
+        if (!generic_instance_exists(lc)) { err = "vrh_render: no generic-primitive instance of this kernel"; return VRH_ERR_UNSUPPORTED; }
+    }
     // AO tail sharing needs several waves per block (they share LDS): 4 unless the block is set.
     // It has instances for uncounted one-frame AO launches at 5 waves / SIMD only: where there is no
-    // SHARE instance the option changes nothing, not even the block size
-    lc.share = opt.share == 1;
+    // SHARE instance the option changes nothing, not even the block size (a generic-primitive scene has none)
+    lc.share = opt.share == 1 && !in.generic;
     lc.share = lc.share && instance_exists(lc);
     lc.block = opt.block ? opt.block : lc.share ? 256 : 64;
     // auto: the LDS part of the stack shrinks (in steps of 4 entries) while LDS, not registers,
@@ -290,7 +352,7 @@ inline int plan_launch(const launch_inputs& in, const launch_device& dev, launch
     // (the primary / AO step loops at their default register budgets have overflow-stack instances;
     // every other kernel keeps its whole stack in LDS, as does an explicit VRH_OPT_STACK_CAP >= depth)
     lc.spill = true;
-    lc.spill = instance_exists(lc) && (!opt.stack || cap < total);
+    lc.spill = !in.generic && instance_exists(lc) && (!opt.stack || cap < total);
     if (lc.spill && !opt.stack)
     {
         launch_config lo = lc;

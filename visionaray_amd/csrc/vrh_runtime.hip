@@ -275,7 +275,15 @@ VRH_API int vrh_scene_upload(vrh_ctx* ctx, const void* nodes_v, uint32_t num_nod
 {
     VRH_CHECK(ctx && out && nodes_v && prims_v, "vrh_scene_upload: null argument");
     VRH_CHECK(num_nodes >= 1 && num_prims >= 1, "vrh_scene_upload: empty BVH");
-    VRH_CHECK(prim_kind == VRH_PRIM_TRI64 || prim_kind == VRH_PRIM_SPHERE48, "vrh_scene_upload: unknown prim_kind");
+    VRH_CHECK(prim_record_bytes(prim_kind) != 0u, "vrh_scene_upload: unknown prim_kind");
+    if (prim_kind == VRH_PRIM_GENERIC80)
+        for (uint32_t i = 0; i < num_prims; ++i)
+        {
+            const uint32_t ty = static_cast<const generic80*>(prims_v)[i].type;
+            VRH_CHECK(ty == VRH_GENERIC_TYPE_TRI || ty == VRH_GENERIC_TYPE_SPHERE,
+                      "vrh_scene_upload: generic primitive " + std::to_string(i) + " has type index " + std::to_string(ty)
+                          + " (1 triangle, 2 sphere)");
+        }
     VRH_CHECK(num_nodes % 2 == 1, "vrh_scene_upload: node count must be odd (root + child pairs)");
     *out = nullptr;
     if (!indices) num_indices = num_prims;
@@ -376,7 +384,9 @@ VRH_API int vrh_scene_upload(vrh_ctx* ctx, const void* nodes_v, uint32_t num_nod
     }
 
     // -- leaf-ordered primitives with END flags
-    const uint32_t f4_per = prim_kind == VRH_PRIM_TRI64 ? 3u : 2u;
+    // (a generic primitive takes the triangle's three words whichever alternative it holds: vrh_internal.h
+    // generic_leaf_record)
+    const uint32_t f4_per = prim_kind == VRH_PRIM_SPHERE48 ? 2u : 3u;
     std::vector<float4> lp(size_t(f4_per) * num_indices);
     for (uint32_t i = 0; i < num_indices; ++i)
     {
@@ -393,6 +403,12 @@ VRH_API int vrh_scene_upload(vrh_ctx* ctx, const void* nodes_v, uint32_t num_nod
             std::memcpy(&w[0], &t.e2[2], 4);
             w[1] = t.prim_id; w[2] = t.geom_id; w[3] = flags;
             std::memcpy(&q[2], w, 16);
+        }
+        else if (prim_kind == VRH_PRIM_GENERIC80)
+        {
+            uint32_t w[12];
+            generic_leaf_record(static_cast<const generic80*>(prims_v)[src], end_flag[i] != 0, w);   // types checked above
+            std::memcpy(q, w, 48);
         }
         else
         {
@@ -412,7 +428,7 @@ VRH_API int vrh_scene_upload(vrh_ctx* ctx, const void* nodes_v, uint32_t num_nod
     for (uint32_t i = 0; i < num_prims; ++i)
     {
         uint32_t ids[2];
-        std::memcpy(ids, static_cast<const uint8_t*>(prims_v) + size_t(i) * (prim_kind == VRH_PRIM_TRI64 ? 64u : 48u), 8);
+        std::memcpy(ids, static_cast<const uint8_t*>(prims_v) + size_t(i) * prim_record_bytes(prim_kind), 8);
         max_geom_id = std::max(max_geom_id, ids[0]);
         max_prim_id = std::max(max_prim_id, ids[1]);
     }
@@ -581,6 +597,11 @@ VRH_API int vrh_scene_list_create(vrh_ctx* ctx, const vrh_scene* const* scenes, 
         const vrh_scene* m = scenes[i];
         VRH_CHECK(m && m->ctx == ctx, "vrh_scene_list_create: scene missing or of another context");
         VRH_CHECK(m->num_roots == 1, "vrh_scene_list_create: members must be single BVHs");
+        if (m->info.prim_kind == VRH_PRIM_GENERIC80)
+        {
+            set_error("vrh_scene_list_create: BVH lists take triangle or sphere scenes, not generic-primitive scenes");
+            return VRH_ERR_UNSUPPORTED;
+        }
         VRH_CHECK(m->info.prim_kind == kind, "vrh_scene_list_create: members must share one primitive type");
         pairs += m->num_pairs;
         prims += m->info.num_indices;
@@ -654,6 +675,11 @@ VRH_API int vrh_scene_build(vrh_ctx* ctx, const void* prims, uint32_t num_prims,
                             const void* face_normals, const vrh_build_desc* desc, vrh_scene** out)
 {
     VRH_CHECK(ctx && prims && out && num_prims >= 1, "vrh_scene_build: bad argument");
+    if (prim_kind == VRH_PRIM_GENERIC80)
+    {
+        set_error("vrh_scene_build: the LBVH build takes triangles or spheres, not generic primitives (build with vrh_build_bvh and upload)");
+        return VRH_ERR_UNSUPPORTED;
+    }
     VRH_CHECK(prim_kind == VRH_PRIM_TRI64 || prim_kind == VRH_PRIM_SPHERE48, "vrh_scene_build: unknown prim_kind");
     VRH_CHECK(!desc || desc->method == VRH_BUILD_LBVH, "vrh_scene_build: unknown build method");
     *out = nullptr;
@@ -747,6 +773,11 @@ VRH_API int vrh_bvh_sah_cost(const void* nodes_v, uint32_t num_nodes, float ci, 
 VRH_API int vrh_scene_set_vertex_normals(vrh_scene* sc, const void* normals, uint32_t num_normals)
 {
     VRH_CHECK(sc && normals, "vrh_scene_set_vertex_normals: null argument");
+    if (sc->info.prim_kind == VRH_PRIM_GENERIC80)
+    {
+        set_error("vrh_scene_set_vertex_normals: generic-primitive scenes take per-face normals only");
+        return VRH_ERR_UNSUPPORTED;
+    }
     VRH_CHECK(sc->info.prim_kind == VRH_PRIM_TRI64, "vrh_scene_set_vertex_normals: triangles only");
     VRH_CHECK(uint64_t(num_normals) >= 3ull * (uint64_t(sc->info.max_prim_id) + 1ull),
               "vrh_scene_set_vertex_normals: need 3 normals per prim_id (3 * (max prim_id + 1))");
@@ -1321,6 +1352,16 @@ int validate_render(vrh_ctx* ctx, const vrh_scene* sc, vrh_rt* rt, const vrh_cam
             set_error("vrh_render: a generic shading (vrh_shading_create_generic) is taken by VRH_KERNEL_PATHTRACING only");
             return VRH_ERR_UNSUPPORTED;
         }
+        if (sc->info.prim_kind == VRH_PRIM_GENERIC80)
+        {
+            // generic primitives: simple and whitted with per-face normals (the plan names what else is asked for)
+            if (k->normal_binding == VRH_NORMALS_PER_VERTEX)
+            {
+                set_error("vrh_render: generic-primitive scenes do not support per-vertex normals");
+                return VRH_ERR_UNSUPPORTED;
+            }
+        }
+        else
         if (sc->info.prim_kind != VRH_PRIM_TRI64) { set_error("vrh_render: the shading kernels support triangles"); return VRH_ERR_UNSUPPORTED; }
         if (list) { set_error("vrh_render: the shading kernels take a single BVH (scene lists: primary and AO kernels)"); return VRH_ERR_UNSUPPORTED; }
         VRH_CHECK(k->shading->num_materials > sc->info.max_geom_id, "vrh_render: a geom_id has no material");
@@ -1355,6 +1396,11 @@ int validate_render(vrh_ctx* ctx, const vrh_scene* sc, vrh_rt* rt, const vrh_cam
     }
     rows.sh = shard ? *shard : vrh_shard{ 0, 1, 0, 0 };
     VRH_CHECK(rows.sh.count >= 1 && rows.sh.index < rows.sh.count, "vrh_render: bad shard");
+    if (sc->info.prim_kind == VRH_PRIM_GENERIC80 && (rows.sh.count > 1 || rows.sh.packed))
+    {
+        set_error("vrh_render: generic-primitive scenes do not support shards or render groups (whole frames only)");
+        return VRH_ERR_UNSUPPORTED;
+    }
     rows.local_bands = vrh_shard_bands(cam->height, rows.sh.index, rows.sh.count);
     VRH_CHECK(rt->width == cam->width, "vrh_render: render target width != camera width");
     rows.frame_rows = cam->height;
@@ -1383,6 +1429,7 @@ int plan_render(const vrh_ctx* ctx, const vrh_scene* sc, uint32_t num_frames, co
     in.generic_shading = k->shading && k->shading->gmaterials;
     in.textured = k->shading && k->shading->num_textures != 0 && k->kind != VRH_KERNEL_PRIMARY && k->kind != VRH_KERNEL_AO;
     in.sampler_pass = sampler_pass; in.hit_mask = k->hit_mask != nullptr; in.num_frames = num_frames;
+    in.generic = sc->info.prim_kind == VRH_PRIM_GENERIC80;
     in.prim_kind = sc->info.prim_kind; in.max_depth = sc->info.max_depth; in.num_roots = sc->num_roots;
     in.device_bytes = sc->info.device_bytes;
     in.finite_bounds = sc->finite_bounds; in.has_quads = sc->quads != nullptr; in.root_is_pair0 = sc->roots[0] == 0u;
@@ -2002,7 +2049,15 @@ VRH_API int vrh_build_bvh(const void* prims, uint32_t num_prims, uint32_t kind, 
 {
     VRH_CHECK(prims && nodes_out && num_nodes_out && indices_out, "vrh_build_bvh: null argument");
     VRH_CHECK(num_prims >= 1, "vrh_build_bvh: no primitives");
-    VRH_CHECK(kind == VRH_PRIM_TRI64 || kind == VRH_PRIM_SPHERE48, "vrh_build_bvh: unknown prim kind");
+    VRH_CHECK(prim_record_bytes(kind) != 0u, "vrh_build_bvh: unknown prim kind");
+    if (kind == VRH_PRIM_GENERIC80)
+        for (uint32_t i = 0; i < num_prims; ++i)
+        {
+            const uint32_t ty = static_cast<const generic80*>(prims)[i].type;
+            VRH_CHECK(ty == VRH_GENERIC_TYPE_TRI || ty == VRH_GENERIC_TYPE_SPHERE,
+                      "vrh_build_bvh: generic primitive " + std::to_string(i) + " has type index " + std::to_string(ty)
+                          + " (1 triangle, 2 sphere)");
+        }
     try
     {
         return build_bvh(prims, num_prims, kind, static_cast<node32*>(nodes_out), num_nodes_out, indices_out, max_depth_out);

@@ -102,9 +102,52 @@ __device__ inline surface_t get_surface(const shade_params& S, const float4* __r
     return sf;
 }
 
+// get_surface for a hit in a generic_primitive<triangle, sphere> BVH (VRH_PRIM_GENERIC80; get_surface.h through
+// get_normal_dispatch and detail/generic_primitive_get_normal.h), per-face normal binding: a triangle takes
+// normals[prim_id], a sphere (isect_pos - center) / radius with true divisions (get_normal.h:135-138,
+// vector3.inl:200-203) -- its entry of `normals` is never read.  The shading normal is the geometric normal.
+__device__ inline surface_t get_surface_generic(const shade_params& S, const float4* __restrict__ prims,
+                                                const float4* __restrict__ normals, uint32_t prim_id, uint32_t li, f3 pos)
+{
+    surface_t sf;
+    const float4* q = prims + 3u * li;
+    const float4 qc = q[2];
+    sf.mi = __float_as_uint(qc.z);
+    sf.m = S.materials[sf.mi];
+    if (__float_as_uint(qc.w) & SPHERE_BIT)
+    {
+        const float4 qa = q[0];
+        sf.gn = sf.sn = mk3((pos.x - qa.x) / qa.w, (pos.y - qa.y) / qa.w, (pos.z - qa.z) / qa.w);
+    }
+    else
+    {
+        const float4 nn = normals[prim_id];                            // get_normal.h:26-37
+        sf.gn = sf.sn = mk3(nn.x, nn.y, nn.z);
+    }
+    return sf;
+}
+
+// The device powf is v_log_f32, a multiply, v_exp_f32, and v_exp_f32 returns 0 for a result below FLT_MIN.  The host's
+// powf returns the denormal, which reaches the image where a channel has no diffuse part (the reference example's
+// pure colours under exponent 128).  SUBNORMAL: a zero result is formed again as the square of x^(y/2), an IEEE
+// product that rounds into the denormal range as any other (and stays 0 where x^y rounds to 0); every other result
+// is the builtin's, bit for bit.  Only the generic-primitive instances ask for it: the others keep their code.
+template <bool SUBNORMAL>
+__device__ __forceinline__ float shade_powf(float x, float y)
+{
+    float r = __builtin_powf(x, y);
+    if constexpr (SUBNORMAL)
+        if (r == 0.0f)
+        {
+            const float h = __builtin_powf(x, y * 0.5f);
+            r = h * h;
+        }
+    return r;
+}
+
 // plastic::shade (plastic.inl:21-37) for one point light: pi * (lambertian + blinn) * intensity * ndotl
 // (TEX: the diffuse term is tex_color * lambertian.f, plastic.inl:180-183)
-template <bool TEX = false>
+template <bool TEX = false, bool SUBNORMAL = false>
 __device__ inline f3 plastic_shade(const plastic_t& m, f3 n, f3 wo, f3 pos, const point_light_t& L, uint32_t tex = TEX_ONE)
 {
     constexpr float PI = 3.14159265358979323846264338328e+00f;      // math.h:240 constants::pi
@@ -119,10 +162,10 @@ __device__ inline f3 plastic_shade(const plastic_t& m, f3 n, f3 wo, f3 pos, cons
     const float hdotn = tmax(0.0f, dot(h, n));
     const f3 spec = mk3(m.cs[0], m.cs[1], m.cs[2]) * m.ks;
     const float sat = tmax(0.0f, tmin(dot(wi, h), 1.0f));              // saturate, math.h:454-457
-    const float p5 = __builtin_powf(1.0f - sat, 5.0f);
+    const float p5 = shade_powf<SUBNORMAL>(1.0f - sat, 5.0f);
     const f3 schlick = spec + mk3(1.0f - spec.x, 1.0f - spec.y, 1.0f - spec.z) * p5;
     const float nfactor = (m.exp + 2.0f) / (8.0f * PI);
-    const f3 bl = (schlick * nfactor) * __builtin_powf(hdotn, m.exp);
+    const f3 bl = (schlick * nfactor) * shade_powf<SUBNORMAL>(hdotn, m.exp);
     // point_light::intensity, point_light.inl:12-28
     const f3 dv = lpos - pos;
     const float dist = __builtin_sqrtf(dot(dv, dv));
@@ -133,20 +176,24 @@ __device__ inline f3 plastic_shade(const plastic_t& m, f3 n, f3 wo, f3 pos, cons
 }
 
 // colour of a closest hit, simple.inl:32-69 (the miss colour is the caller's)
-template <bool TEX = false>
+// (GEN: the scene holds generic primitives -- get_surface_generic; untextured)
+template <bool TEX = false, bool GEN = false>
 __device__ inline float4 shade_simple(const shade_params& S, const float4* __restrict__ prims,
                                       const float4* __restrict__ normals, const ray_t& r, float t,
                                       uint32_t prim_id, const hit_extra& hx)
 {
     const f3 pos = r.ori + r.dir * t;                                  // simple.inl:37
-    const surface_t sf = get_surface<false, TEX>(S, prims, normals, prim_id, hx.li, hx.u, hx.v);
+    const surface_t sf = [&]() __attribute__((always_inline)) {
+        if constexpr (GEN) return get_surface_generic(S, prims, normals, prim_id, hx.li, pos);
+        else return get_surface<false, TEX>(S, prims, normals, prim_id, hx.li, hx.u, hx.v);
+    }();
     // plastic.inl:13-16 ambient() = ca * ka, times from_rgba(ambient_color) (spectrum.inl:375-378)
     const f3 amb = mk3(S.amb[0], S.amb[1], S.amb[2]);
     f3 shaded = (mk3(sf.m.ca[0], sf.m.ca[1], sf.m.ca[2]) * sf.m.ka) * amb;
     const f3 view = neg(r.dir);
     const f3 n = dot(sf.gn, view) < 0.0f ? neg(sf.sn) : sf.sn;       // faceforward, vector.inl:674-681
     for (uint32_t li = 0; li < S.num_lights; ++li)
-        shaded = shaded + plastic_shade<TEX>(sf.m, n, view, pos, S.lights[li], sf.tex);   // simple.inl:63
+        shaded = shaded + plastic_shade<TEX, GEN>(sf.m, n, view, pos, S.lights[li], sf.tex);   // simple.inl:63
     return make_float4(shaded.x, shaded.y, shaded.z, 1.0f);           // to_rgba
 }
 
@@ -178,13 +225,17 @@ constexpr uint32_t WL_POS = 0, WL_N = 3, WL_VIEW = 6, WL_SHADED = 9, WL_WORDS = 
 // (TEX: *tex receives the bounce's packed texture sample, which every light of the bounce reads while its
 // shadow ray is in flight: one more register of lane state, kept outside whitted_lane so that the
 // untextured instances keep their code)
-template <bool TEX = false>
+template <bool TEX = false, bool GEN = false>
 __device__ inline void whitted_surface(const shade_params& S, const float4* __restrict__ prims,
                                        const float4* __restrict__ normals, whitted_lane& w, const ray_t& r, float t,
                                        uint32_t prim_id, const hit_extra& hx, uint32_t* tex = nullptr)
 {
-    w.st3(WL_POS, r.ori + r.dir * t);
-    const surface_t sf = get_surface<false, TEX>(S, prims, normals, prim_id, hx.li, hx.u, hx.v);
+    const f3 pos = r.ori + r.dir * t;
+    w.st3(WL_POS, pos);
+    const surface_t sf = [&]() __attribute__((always_inline)) {
+        if constexpr (GEN) return get_surface_generic(S, prims, normals, prim_id, hx.li, pos);
+        else return get_surface<false, TEX>(S, prims, normals, prim_id, hx.li, hx.u, hx.v);
+    }();
     w.mi = sf.mi;
     if constexpr (TEX) *tex = sf.tex;
     const f3 amb = mk3(S.amb[0], S.amb[1], S.amb[2]);
@@ -220,11 +271,11 @@ __device__ inline ray_t whitted_shadow_ray(const shade_params& S, const whitted_
 }
 
 // a shadow ray ended: add the light's plastic::shade unless occluded (select(active, clr, 0))
-template <bool TEX = false>
+template <bool TEX = false, bool GEN = false>
 __device__ inline void whitted_light_done(const shade_params& S, whitted_lane& w, bool occluded, uint32_t tex = TEX_ONE)
 {
     const f3 c = occluded ? mk3(0.0f, 0.0f, 0.0f)
-               : plastic_shade<TEX>(S.materials[w.mi], w.ld3(WL_N), w.ld3(WL_VIEW), w.ld3(WL_POS), S.lights[w.li], tex);
+               : plastic_shade<TEX, GEN>(S.materials[w.mi], w.ld3(WL_N), w.ld3(WL_VIEW), w.ld3(WL_POS), S.lights[w.li], tex);
     w.st3(WL_SHADED, w.ld3(WL_SHADED) + c);
     w.li += 1u;
 }
