@@ -24,9 +24,14 @@ TRI_DTYPE = np.dtype([("geom_id", "<u4"), ("prim_id", "<u4"), ("pad", "<u4", 2),
 SPHERE_DTYPE = np.dtype([("geom_id", "<u4"), ("prim_id", "<u4"), ("pad", "<u4", 2),
                          ("center", "<f4", 4), ("radius", "<f4"), ("pad2", "<f4", 3)])
 NODE_DTYPE = np.dtype([("bmin", "<f4", 3), ("first", "<u4"), ("bmax", "<f4", 3), ("num_prims", "<u4")])
+# generic_primitive<triangle, sphere> (vrh_oracle.h vo_generic): a TRI_DTYPE or SPHERE_DTYPE record's bytes at 0,
+# the type index at 64 (1 triangle, 2 sphere)
+GENERIC_DTYPE = np.dtype([("data", "u1", 64), ("type", "<u4"), ("pad", "<u4", 3)])
 assert TRI_DTYPE.itemsize == 64 and SPHERE_DTYPE.itemsize == 48 and NODE_DTYPE.itemsize == 32
+assert GENERIC_DTYPE.itemsize == 80
 
-VO_TRI, VO_SPHERE = 0, 1
+VO_TRI, VO_SPHERE, VO_GENERIC = 0, 1, 2
+VO_GENERIC_TRI, VO_GENERIC_SPHERE = 1, 2
 VO_MODE_PRIMARY, VO_MODE_AO, VO_MODE_SIMPLE, VO_MODE_MULTI_HIT, VO_MODE_WHITTED = 0, 1, 2, 3, 4
 VO_MODE_PATHTRACING = 5
 VO_NORMALS_PER_FACE, VO_NORMALS_PER_VERTEX = 0, 1
@@ -216,6 +221,8 @@ def scene_camera(name, W=None, H=None):
 
 @dataclass
 class Scene:
+    """prims: TRI_DTYPE (VO_TRI), SPHERE_DTYPE (VO_SPHERE) or 80-byte generic records (VO_GENERIC: GENERIC_DTYPE
+    or any array of that layout); normals: one row per prim_id (a generic scene's sphere rows are never read)"""
     name: str
     kind: int
     prims: np.ndarray

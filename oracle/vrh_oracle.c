@@ -303,18 +303,35 @@ static void build_rec(builder* B, size_t index, const leaf_info* leaf, int max_l
     }
 }
 
+/* record i of a primitive list: its bytes, and whether they hold a triangle.  A VO_GENERIC record is the
+ * reference's generic_primitive<triangle, sphere> (generic_primitive.h over variant.h:83-143: the alternative's
+ * bytes at 0, the u32 type index at 64: 1 the first alternative, 2 the second), 80 bytes */
+static inline const void* prim_at(const void* prims, int kind, size_t i, int* is_tri)
+{
+    if (kind == VO_GENERIC) {
+        const vo_generic* g = (const vo_generic*)prims + i;
+        *is_tri = g->type == VO_GENERIC_TRI;
+        return g->data;
+    }
+    *is_tri = kind == VO_TRI;
+    return kind == VO_TRI ? (const void*)((const vo_tri*)prims + i) : (const void*)((const vo_sphere*)prims + i);
+}
+
+/* get_bounds of a generic primitive is its alternative's (detail/generic_primitive.inl:41-54, 113-116) */
 static box prim_bounds(const void* prims, int kind, size_t i)
 {
     box b;
     box_invalidate(&b);
-    if (kind == VO_TRI) {                  /* triangle.inl:34-44 */
-        const vo_tri* t = (const vo_tri*)prims + i;
+    int is_tri;
+    const void* rec = prim_at(prims, kind, i, &is_tri);
+    if (is_tri) {                          /* triangle.inl:34-44 */
+        const vo_tri* t = (const vo_tri*)rec;
         v3 v1 = ld(&t->v1);
         box_insert_v(&b, v1);
         box_insert_v(&b, add(v1, ld(&t->e1)));
         box_insert_v(&b, add(v1, ld(&t->e2)));
     } else {                               /* sphere.inl:29-38: center -/+ radius */
-        const vo_sphere* s = (const vo_sphere*)prims + i;
+        const vo_sphere* s = (const vo_sphere*)rec;
         v3 c = ld(&s->center);
         float r = s->radius;
         box_insert_v(&b, mk(c.x - r, c.y - r, c.z - r));
@@ -498,10 +515,12 @@ vo_hit vo_intersect_masked(const float ori_[3], const float dir_[3], const vo_no
         }
         if (terminated) continue;
         for (uint32_t i = node->first; i != node->first + node->num_prims; ++i) {
-            prim_hit hr = kind == VO_TRI ? isect_tri(ori, dir, (const vo_tri*)prims + indices[i])
-                                         : isect_sphere(ori, dir, (const vo_sphere*)prims + indices[i]);
+            int is_tri;
+            const void* rec = prim_at(prims, kind, indices[i], &is_tri);
+            /* a generic primitive intersects as its alternative (detail/generic_primitive.inl:14-31, 98-103) */
+            prim_hit hr = is_tri ? isect_tri(ori, dir, (const vo_tri*)rec) : isect_sphere(ori, dir, (const vo_sphere*)rec);
             ++nprim;
-            if (mask && kind == VO_TRI && hr.hit) hr.hit = mask_keep(mask, hr.prim_id, hr.u, hr.v);
+            if (mask && is_tri && hr.hit) hr.hit = mask_keep(mask, hr.prim_id, hr.u, hr.v);
             /* update_if.h:48-56,73-79 is_closer + update_if.h:27-37 + hit_record.h:54-64 */
             int closer = hr.hit && hr.t >= 0.0f && hr.t < res.t && hr.t < max_t;
             if (!closer) continue;
@@ -571,10 +590,12 @@ int vo_intersect_multi_masked(const float ori_[3], const float dir_[3], const vo
         }
         if (terminated) continue;
         for (uint32_t i = node->first; i != node->first + node->num_prims; ++i) {
-            prim_hit hr = kind == VO_TRI ? isect_tri(ori, dir, (const vo_tri*)prims + indices[i])
-                                         : isect_sphere(ori, dir, (const vo_sphere*)prims + indices[i]);
+            int is_tri;
+            const void* rec = prim_at(prims, kind, indices[i], &is_tri);
+            /* a generic primitive intersects as its alternative (detail/generic_primitive.inl:14-31, 98-103) */
+            prim_hit hr = is_tri ? isect_tri(ori, dir, (const vo_tri*)rec) : isect_sphere(ori, dir, (const vo_sphere*)rec);
             ++nprim;
-            if (mask && kind == VO_TRI && hr.hit) hr.hit = mask_keep(mask, hr.prim_id, hr.u, hr.v);
+            if (mask && is_tri && hr.hit) hr.hit = mask_keep(mask, hr.prim_id, hr.u, hr.v);
             int closer = 0;
             for (int k = 0; k < n && !closer; ++k)
                 closer = hr.hit && hr.t >= 0.0f && hr.t < res[k].t && hr.t < FLT_MAX;
@@ -694,6 +715,34 @@ static vo_hit trace(const vo_scene* s, const float o[3], const float d[3], int a
     }
     return res;
 }
+/* the per-face normal of a hit at isect_pos: normals[prim_id] (get_normal.h:26-37); a sphere held by a generic
+ * primitive takes (isect_pos - center) / radius instead (get_surface through get_normal_dispatch and
+ * detail/generic_primitive_get_normal.h to get_normal.h:135-138; vector3.inl:200-203: three true divisions),
+ * and its row of `normals` is never read.  The hit's record is primitive(list_index). */
+static v3 face_normal(const vo_scene* s, const vo_hit* hr, v3 isect_pos)
+{
+    if (s->kind == VO_GENERIC) {
+        int is_tri;
+        const void* rec = prim_at(s->prims, s->kind, s->indices[hr->list_index], &is_tri);
+        if (!is_tri) {
+            const vo_sphere* sp = (const vo_sphere*)rec;
+            v3 d = sub(isect_pos, ld(&sp->center));
+            return mk(d.x / sp->radius, d.y / sp->radius, d.z / sp->radius);
+        }
+    }
+    return ld(&s->normals[hr->prim_id]);
+}
+
+/* what the oracle has no restatement of on a generic-primitive scene (the product refuses the same): BVH
+ * lists, the per-vertex normal binding and the path tracer */
+static int generic_unsupported(const vo_scene* s, const vo_kernel* k)
+{
+    if (s->kind != VO_GENERIC) return 0;
+    return s->next != NULL || k->mode == VO_MODE_PATHTRACING
+        || ((k->mode == VO_MODE_SIMPLE || k->mode == VO_MODE_WHITTED || k->mode == VO_MODE_MULTI_HIT)
+            && k->normal_binding != VO_NORMALS_PER_FACE);
+}
+
 static void shade_simple(const vo_scene* s, const vo_kernel* k, v3 ori, v3 dir, const vo_hit* hr, float out[4]);
 static void shade_whitted(const vo_scene* s, const vo_kernel* k, v3 ori, v3 dir, vo_hit hr, float out[4],
                           uint32_t* rays, vo_counters* cnt);
@@ -730,7 +779,7 @@ static px_out shade_pixel_at(const vo_scene* s, const vo_camera* cam, const vo_k
         return o;
     }
     v3 isect_pos = add(ori, muls(dir, hr.t));
-    v3 n = ld(&s->normals[hr.prim_id]);                                /* get_normal.h:26-37 */
+    v3 n = face_normal(s, &hr, isect_pos);
     /* vector3.inl:357-367 make_orthonormal_basis (w = n) */
     v3 bv = fabsf(n.x) > fabsf(n.y) ? normalize(mk(-n.z, 0.0f, n.x)) : normalize(mk(0.0f, n.z, -n.y));
     v3 bu = cross(bv, n);
@@ -764,12 +813,12 @@ static px_out shade_pixel(const vo_scene* s, const vo_camera* cam, const vo_kern
     return shade_pixel_at(s, cam, k, x, y, 0.0f, 0.0f, cnt);
 }
 
-/* get_surface (get_surface.h:336-376, 576-592) of a triangle hit: geometric + shading normal by
+/* get_surface (get_surface.h:336-376, 576-592) of a hit at pos: geometric + shading normal by
  * the normal binding, material by geom_id */
-static const vo_plastic* surface(const vo_scene* s, const vo_kernel* k, const vo_hit* hr, v3* gn, v3* sn)
+static const vo_plastic* surface(const vo_scene* s, const vo_kernel* k, const vo_hit* hr, v3 pos, v3* gn, v3* sn)
 {
     if (k->normal_binding == VO_NORMALS_PER_FACE) {
-        *gn = *sn = ld(&s->normals[hr->prim_id]);                       /* get_normal.h:26-37 */
+        *gn = *sn = face_normal(s, hr, pos);
     } else {
         /* get_surface.h:336-376 -> get_normal(hr, primitive(list_index)) (get_normal.h:110-116)
          * and get_shading_normal.h:64-84 with lerp(a,b,c,u,v) (math.h:466-475) */
@@ -825,7 +874,7 @@ static void shade_simple(const vo_scene* s, const vo_kernel* k, v3 ori, v3 dir, 
 {
     v3 pos = add(ori, muls(dir, hr->t));                               /* simple.inl:37 */
     v3 gn, sn;
-    const vo_plastic* m = surface(s, k, hr, &gn, &sn);
+    const vo_plastic* m = surface(s, k, hr, pos, &gn, &sn);
     v3 shaded = ambient_term(k, m);
     v3 view = mk(-dir.x, -dir.y, -dir.z);
     v3 n = dot(gn, view) < 0.0f ? mk(-sn.x, -sn.y, -sn.z) : sn;          /* vector.inl:674-681 */
@@ -849,7 +898,7 @@ static void shade_whitted(const vo_scene* s, const vo_kernel* k, v3 ori, v3 dir,
     while (hr.hit && thr > k->eps && depth++ < k->num_bounces) {
         v3 pos = add(ori, muls(dir, hr.t));                            /* whitted.inl:223 */
         v3 gn, sn;
-        const vo_plastic* m = surface(s, k, &hr, &gn, &sn);
+        const vo_plastic* m = surface(s, k, &hr, pos, &gn, &sn);
         v3 shaded = ambient_term(k, m);
         v3 view = mk(-dir.x, -dir.y, -dir.z);
         v3 n = dot(gn, view) < 0.0f ? mk(-sn.x, -sn.y, -sn.z) : sn;      /* faceforward */
@@ -1035,7 +1084,7 @@ static void pathtrace_pixel(const vo_scene* s, const vo_camera* cam, const vo_ke
         if (bounce == 0) result_hit = 1;                                /* pathtracing.inl:65-69 */
         v3 view = mk(-dir.x, -dir.y, -dir.z);
         v3 gn, sn;
-        const vo_plastic* m = surface(s, k, &hr, &gn, &sn);            /* pathtracing.inl:77 */
+        const vo_plastic* m = surface(s, k, &hr, add(ori, muls(dir, hr.t)), &gn, &sn); /* pathtracing.inl:77 */
         v3 n = dot(gn, view) < 0.0f ? mk(-sn.x, -sn.y, -sn.z) : sn;      /* faceforward, vector.inl:674-681 */
         v3 refl = mk(0.0f, 0.0f, 0.0f);
         float pdf = 0.0f;
@@ -1083,6 +1132,7 @@ uint64_t vo_render_multi(const vo_scene* s, const vo_camera* cam, const vo_kerne
 {
     int W = cam->width, H = cam->height, n = k->max_hits;
     if (n < 1 || n > VO_MAX_HITS) return 0;
+    if (generic_unsupported(s, k)) return 0;     /* nothing written */
 #ifdef _OPENMP
     if (threads <= 0) threads = omp_get_max_threads();
 #else
@@ -1126,6 +1176,7 @@ uint64_t vo_render_rows(const vo_scene* s, const vo_camera* cam, const vo_kernel
     uint64_t rays = 0, nbox = 0, nprim = 0;
     int W = cam->width;
     const unsigned* sb = cam->scissor;
+    if (generic_unsupported(s, k)) return 0;     /* nothing written, no ray traced */
     const int whole = sb[0] == 0 && sb[1] == 0 && sb[2] == 0 && sb[3] == 0;
     const int cx0 = whole ? 0 : (int)sb[0], cy0 = whole ? 0 : (int)sb[1];
     const int cx1 = whole ? W : (int)(sb[2] < (unsigned)W ? sb[2] : (unsigned)W);
@@ -1200,6 +1251,7 @@ static int64_t render_sampled_impl(const vo_scene* s, const vo_camera* cam, cons
 {
     if (kind == VO_SAMPLER_SSAA && count != 2 && count != 4 && count != 8) return -1;
     if (kind == VO_SAMPLER_SSAA && k->mode == VO_MODE_PATHTRACING) return -1;
+    if (generic_unsupported(s, k)) return -1;    /* nothing written */
     const int n = kind == VO_SAMPLER_SSAA ? count : 1;
     int W = cam->width;
     int cx0, cy0, cx1, cy1;
@@ -1257,6 +1309,7 @@ int64_t vo_render_pathtracing(const vo_scene* s, const vo_camera* cam, const vo_
                               float* color, uint32_t* prim_id, float* t, uint32_t* nrays, uint64_t* sig, int threads)
 {
     if (k->mode != VO_MODE_PATHTRACING) return -1;
+    if (generic_unsupported(s, k)) return -1;    /* nothing written */
     int W = cam->width;
     int cx0, cy0, cx1, cy1;
     scissor_of(cam, &cx0, &cy0, &cx1, &cy1);
@@ -1290,6 +1343,7 @@ uint64_t vo_render_pixels(const vo_scene* s, const vo_camera* cam, const vo_kern
 {
     uint64_t rays = 0;
     int W = cam->width;
+    if (generic_unsupported(s, k)) return 0;     /* nothing written, no ray traced */
 #ifdef _OPENMP
     if (threads <= 0) threads = omp_get_max_threads();
 #else

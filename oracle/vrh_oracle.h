@@ -12,6 +12,9 @@
  * All binary layouts are the reference's:
  *   vo_tri    64 B : geom_id@0 prim_id@4 v1@16 e1@32 e2@48      (basic_triangle<3,float>)
  *   vo_sphere 48 B : geom_id@0 prim_id@4 center@16 radius@32     (basic_sphere<float>)
+ *   vo_generic 80 B: a vo_tri or a vo_sphere @0, type index @64: 1 triangle, 2 sphere
+ *                    (generic_primitive<basic_triangle<3,float>, basic_sphere<float>>; tests/golden/generic_primitive_ref.cpp
+ *                    asserts the layout against the reference's own type)
  *   vo_node   32 B : bbox_min[3] first_child|first_prim bbox_max[3] num_prims   (bvh.h:52-119)
  */
 #ifndef VRH_ORACLE_H
@@ -28,8 +31,17 @@ typedef struct { float x, y, z, pad; } vo_vec3;                         /* vecto
 typedef struct { uint32_t geom_id, prim_id, pad0, pad1; vo_vec3 v1, e1, e2; } vo_tri;
 typedef struct { uint32_t geom_id, prim_id, pad0, pad1; vo_vec3 center; float radius, pad2, pad3, pad4; } vo_sphere;
 typedef struct { float bmin[3]; uint32_t first; float bmax[3]; uint32_t num_prims; } vo_node;
+typedef struct { unsigned char data[64]; uint32_t type, pad0, pad1, pad2; } vo_generic;
 
-enum { VO_TRI = 0, VO_SPHERE = 1 };
+/* the kind of a primitive list.  VO_GENERIC: triangles and spheres in one list and one BVH, as vo_generic records.
+ * The builder takes each record's bounds from its alternative and both leaf loops intersect it as its alternative
+ * (the hit mask applies to triangles only); the per-face normal of a sphere hit -- AO, simple, every bounce of
+ * whitted -- is (isect_pos - center) / radius (get_normal.h:135-138) instead of normals[prim_id], whose sphere rows
+ * are never read.  BVH lists, the per-vertex normal binding and the path tracer have no restatement over generic
+ * records: vo_render_rows / vo_render_pixels / vo_render_multi then return 0 (an image traces at least one ray),
+ * vo_render_sampled / vo_render_sampled_paths / vo_render_pathtracing -1, and write nothing. */
+enum { VO_TRI = 0, VO_SPHERE = 1, VO_GENERIC = 2 };
+enum { VO_GENERIC_TRI = 1, VO_GENERIC_SPHERE = 2 };
 enum { VO_MODE_PRIMARY = 0, VO_MODE_AO = 1, VO_MODE_SIMPLE = 2, VO_MODE_MULTI_HIT = 3, VO_MODE_WHITTED = 4,
        VO_MODE_PATHTRACING = 5 };
 enum { VO_MAX_HITS = 16 };

@@ -10,6 +10,10 @@
 // primary / AO / simple / whitted on one frame, one BVH and nothing else asked for are refused only for LDS.
 // Then spot-checks that inputs with generic = false give the plans tests/golden/launch_plan.txt records (named
 // cases printed in its format; tests/test_launch_plan_generic.py looks them up there).
+//
+// `launch_plan_generic_check limits` prints instead, per kernel (primary, ao, simple, whitted) at default options, the
+// greatest BVH depth plan_launch accepts for a generic scene -- every depth up to it is accepted, the next one is
+// refused for LDS -- as lines "<kernel> <depth>" (tests/gp_cases.py DEPTH_LIMIT records them).
 #include "../../visionaray_amd/csrc/vrh_launch.h"
 
 #include <cstdio>
@@ -181,10 +185,42 @@ void plain_cases()
             }
 }
 
+// the deepest generic BVH each kernel takes at default options
+int limits()
+{
+    const mode none{ false, false, false, false, false };
+    const std::pair<const char*, uint32_t> kernels[] = { { "primary", VRH_KERNEL_PRIMARY }, { "ao", VRH_KERNEL_AO },
+                                                          { "simple", VRH_KERNEL_SIMPLE }, { "whitted", VRH_KERNEL_WHITTED } };
+    for (const auto& k : kernels)
+    {
+        const family f{ k.first, k.second, false, true };
+        uint32_t limit = 0;
+        for (uint32_t depth = 1; depth <= 1024; ++depth)
+        {
+            launch_plan p{};
+            std::string err;
+            const int rc = plan_launch(inputs(f, none, 1, depth, false, true), model_device{}, p, err);
+            const auto line = [&] { return std::string(k.first) + " depth " + std::to_string(depth) + ": " + describe(rc, p, err); };
+            if (!rc)
+            {
+                REQUIRE(limit + 1 == depth, "every depth up to the limit is accepted");
+                REQUIRE(uint32_t(p.cfg.stack_cap) == p.stack_total && p.stack_total >= depth && !p.cfg.spill, "the whole stack in LDS");
+                REQUIRE(model_device{}.lds_bytes(p.cfg) <= CU_LDS, "LDS of a CU");
+                limit = depth;
+            }
+            else
+                REQUIRE(rc == VRH_ERR_UNSUPPORTED && err.find("LDS") != std::string::npos, "a deeper tree is refused for LDS");
+        }
+        std::printf("%s %u\n", k.first, limit);
+    }
+    return 0;
+}
+
 } // namespace
 
-int main()
+int main(int argc, char** argv)
 {
+    if (argc > 1 && std::string(argv[1]) == "limits") return limits();
     plain_cases();
     return sweep();
 }

@@ -18,6 +18,9 @@ Cases, each a function of its seed alone, 60 x 44 pixels (partial 8 x 8 tiles on
   gp_soup     150 random triangles and 150 random spheres, interleaved in prim order, geom_id = prim_id % 4
   gp_inside   the camera inside one large sphere that encloses a few triangles and small spheres: the large
               sphere's nearer root is behind the origin (t < 0, rejected), so its pixels miss
+  gp_sweep    the scene generator of the randomized GPU sweep (tests/gp_cases.py sweep_scene / sweep_shading /
+              sweep_camera) at fewer primitives: 160 triangles with sizes from 1e-3 to 0.3, some of them slivers,
+              120 spheres of radius 1e-3 to 0.2 that overlap, the camera inside the cloud, one to three lights
 Every .npz is self-contained: the 80-byte records (20 u32 words), the reference's nodes and indices, normals
 (one row per prim_id; a sphere's row is never read and stays 0), plastic materials (13 floats), lights (10
 floats), the camera basis (eye, u, v, w), and per pixel prim_id / t (primary), occ / ao_color (AO, the
@@ -47,7 +50,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, HERE)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 import visionaray_amd as va  # noqa: E402
+from gp_cases import random_plastics, sweep_camera, sweep_scene, sweep_shading  # noqa: E402
 from make_pathtrace_golden import save_npz  # noqa: E402
 
 BIN = os.path.join(ROOT, "oracle", "_ref", "generic_primitive_ref")
@@ -58,7 +63,7 @@ AMBIENT = (1.0, 1.0, 1.0, 1.0)
 AO_SAMPLES, AO_EPS = 8, 1e-3
 MIN_SHARE = 0.05
 # case, first seed
-CASES = [("gp_example", 100), ("gp_soup", 200), ("gp_inside", 300)]
+CASES = [("gp_example", 100), ("gp_soup", 200), ("gp_inside", 300), ("gp_sweep", 400)]
 
 
 def compile_generator(ref):
@@ -74,12 +79,6 @@ def camera_basis(eye, center, fovy):
     cam.look_at(tuple(float(x) for x in eye), tuple(float(x) for x in center))
     b = cam.basis(W, H)
     return np.float32([list(b.eye), list(b.cam_u), list(b.cam_v), list(b.cam_w)])
-
-
-def random_plastics(rng, n):
-    return np.stack([va.plastic(ca=rng.uniform(0.0, 0.3, 3), ka=rng.uniform(0.3, 1.0), cd=rng.uniform(0.2, 0.9, 3),
-                                kd=rng.uniform(0.5, 1.0), cs=rng.uniform(0.3, 1.0, 3), ks=rng.uniform(0.2, 0.8),
-                                exp=float(rng.choice([8.0, 16.0, 32.0, 64.5]))) for _ in range(n)])
 
 
 def example_scene(seed):
@@ -153,7 +152,17 @@ def inside_scene(seed):
     return prims, tris, random_plastics(rng, 3), lights, basis, dict(bounces=3, eps=1e-3, ao_radius=0.5)
 
 
-SCENES = {"gp_example": example_scene, "gp_soup": soup_scene, "gp_inside": inside_scene}
+def sweep_fixture_scene(seed):
+    rng = np.random.default_rng(seed)
+    prims, tris, _ = sweep_scene(rng, 160, 120)
+    b = sweep_camera(rng, W, H, inside=True).basis(W, H)
+    basis = np.float32([list(b.eye), list(b.cam_u), list(b.cam_v), list(b.cam_w)])
+    mats, lights = sweep_shading(rng)
+    return prims, tris, mats, lights, basis, dict(bounces=int(rng.integers(2, 6)), eps=float(rng.choice([1e-3, 1e-4])),
+                                                  ao_radius=float(np.float32(10.0 ** rng.uniform(-1.0, 0.0))))
+
+
+SCENES = {"gp_example": example_scene, "gp_soup": soup_scene, "gp_inside": inside_scene, "gp_sweep": sweep_fixture_scene}
 
 
 def run_ref(prims, normals, mats, lights, basis, spec):

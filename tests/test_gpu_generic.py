@@ -141,24 +141,119 @@ def test_equal_t_resolves_in_leaf_order(ctx, order, winner):
     assert out["prim_id"][centre] == winner
 
 
-def test_comb_40_deep_equals_tri64_or_is_refused(ctx):
-    tris, bvh = deep_cases.comb_bvh(41, deep_cases.PITCH)
-    gen = va.index_bvh(va.make_generic(tris, None), bvh.nodes, bvh.indices, 40)
+def comb(depth):
+    """a comb of `depth` levels as TRI64 and as GENERIC80 under the same tree, and the axial camera: a ray crosses
+    every leaf box, so the walk holds a pushed leaf per level"""
+    tris, bvh = deep_cases.comb_bvh(depth + 1, deep_cases.PITCH)
+    gen = va.index_bvh(va.make_generic(tris, None), bvh.nodes, bvh.indices, depth)
     cam = va.camera()
-    L = 40 * deep_cases.PITCH
+    L = depth * deep_cases.PITCH
     cam.perspective(0.8, np.float32(G.W) / np.float32(G.H), 0.001, 1000.0)
-    cam.look_at((L + 1.0, 0.2, 0.2), (0.0, 0.2, 0.2))                      # axial: a ray crosses every leaf box
-    cam = cam.basis(G.W, G.H)
+    cam.look_at((L + 1.0, 0.2, 0.2), (0.0, 0.2, 0.2))
+    return tris, bvh, gen, cam.basis(G.W, G.H)
+
+
+def test_comb_40_deep_equals_tri64_or_is_refused(ctx):
+    """(40 levels are within every kernel's LDS limit, gp_cases.DEPTH_LIMIT: the frames must render)"""
+    tris, bvh, gen, cam = comb(40)
     ml = G.fixture("gp_soup")
     plain = four_frames(ctx, upload(ctx, bvh, tris), cam, ml)
     dev = upload(ctx, gen, tris)
-    assert dev.info["max_depth"] == 40
-    try:
-        got = four_frames(ctx, dev, cam, ml)
-    except va.VrhError as e:
-        assert e.code == _capi.VRH_ERR_UNSUPPORTED
-        return
+    assert dev.info["max_depth"] == 40 < min(G.DEPTH_LIMIT.values())
+    got = four_frames(ctx, dev, cam, ml)
     assert_same_frames(plain, got)
+
+
+DEEP_SPEC = dict(bg=(0.1, 0.2, 0.3, 1.0), ambient=(1.0, 1.0, 1.0, 1.0), ao_samples=8, ao_radius=0.3, ao_eps=1e-3, bounces=3, eps=1e-3)
+
+
+@pytest.mark.parametrize("kind", G.KERNELS)
+def test_comb_at_the_lds_depth_limit_renders(ctx, oracle_mod, kind):
+    """the deepest tree the launch plan accepts for this kernel (tests/test_launch_plan_generic.py pins the number): the
+    whole stack in LDS, all of a CU's 160 KiB in primary visibility and simple.  Against the oracle's frame and against
+    the TRI64 upload of the same tree."""
+    depth = G.DEPTH_LIMIT[kind]
+    tris, bvh, gen, cam = comb(depth)
+    ml = G.fixture("gp_soup")
+    dev = upload(ctx, gen, tris)
+    assert dev.info["max_depth"] == depth
+    sh = G.shading_of(ctx, ml)
+    got = G.render(ctx, dev, cam, G.kernel(kind, dev, sh, DEEP_SPEC))
+    normals = np.zeros((len(tris), 4), np.float32)
+    normals[tris["prim_id"]] = va.face_normals(tris)
+    sc = G.oracle_scene(oracle_mod, "comb%d" % depth, gen.prims, bvh.nodes, bvh.indices, normals, depth)
+    ref = G.oracle_frame(oracle_mod, sc, G.oracle_camera(cam, G.W, G.H), kind, DEEP_SPEC, ml["materials"], ml["lights"])
+    assert (ref["prim_id"] != G.MISS).any() and (ref["prim_id"] == G.MISS).any()
+    G.assert_frame(got, ref, kind, 8, "comb%d" % depth)
+    plain_dev = upload(ctx, bvh, tris)
+    plain = G.render(ctx, plain_dev, cam, G.kernel(kind, plain_dev, sh, DEEP_SPEC))
+    assert_same_frames({kind: plain}, {kind: got}, [kind])
+
+
+@pytest.mark.parametrize("kind", G.KERNELS)
+def test_comb_one_level_past_the_lds_depth_limit_is_refused(ctx, kind):
+    depth = G.DEPTH_LIMIT[kind] + 1
+    tris, bvh, gen, cam = comb(depth)
+    dev = upload(ctx, gen, tris)
+    assert dev.info["max_depth"] == depth
+    sh = G.shading_of(ctx, G.fixture("gp_soup"))
+    rt = va.hip_buffer_rt(ctx, G.W, G.H)
+    mark = np.full((G.W * G.H, 4), 7.0, np.float32)
+    rt.upload(color=mark, prim_id=np.full(G.W * G.H, 12345, np.uint32))
+    with pytest.raises(va.VrhError) as e:
+        va.render(ctx, dev, rt, cam, G.kernel(kind, dev, sh, DEEP_SPEC))
+    assert e.value.code == _capi.VRH_ERR_UNSUPPORTED and "LDS" in str(e.value)
+    ctx.sync()
+    out = rt.download()
+    assert G.same_bits(out["color"], mark) and (out["prim_id"] == 12345).all()
+
+
+@pytest.mark.parametrize("where", ["outside", "inside"])
+def test_sphere_normal_feeds_ao_and_shading_vs_oracle(ctx, oracle_mod, where):
+    """One sphere of radius 0.7 and one triangle that pierces it, 33 x 17 pixels, all four kernels against the oracle.
+    From outside the sphere's normal (isect_pos - center) / radius faces the viewer on every sphere hit.  From inside
+    the sphere the reference's ray / sphere test (math/intersect.h:186-221) returns the nearer root, which lies behind
+    the origin and is rejected (t < 0): no ray that starts inside meets the sphere, as in the fixture gp_inside, so an
+    outward normal that faces away from the viewer cannot arise -- the camera inside sees the triangle through the
+    sphere, and the assertion on the normal's side holds over the sphere hits there are (none)."""
+    w, h = 33, 17
+    tris = va.make_triangles([[-0.2, -0.2, 0.35]], [[1.3, 0.0, 0.0]], [[0.0, 1.3, 0.1]], prim_id=[0], geom_id=[1])
+    sph = va.make_spheres([[0.0, 0.0, 0.0]], [0.7], prim_id=[1], geom_id=[2])
+    gen = va.make_generic(tris, sph)
+    bvh = va.build_index_bvh(gen)
+    cam = va.camera()
+    cam.perspective(0.9, np.float32(w) / np.float32(h), 0.001, 1000.0)
+    if where == "outside":
+        cam.look_at((1.9, 1.4, 2.3), (0.0, 0.0, 0.0))
+    else:
+        cam.look_at((0.1, 0.05, -0.3), (0.3, 0.3, 1.0))
+    cam = cam.basis(w, h)
+    ml = G.fixture("gp_soup")
+    spec = dict(DEEP_SPEC, ao_radius=2.0, bounces=4)
+    dev = upload(ctx, bvh, tris)
+    sh = G.shading_of(ctx, ml)
+    normals = np.zeros((2, 4), np.float32)
+    normals[0] = va.face_normals(tris)[0]
+    sc = G.oracle_scene(oracle_mod, "sphere_normal", gen, bvh.nodes, bvh.indices, normals, bvh.max_depth)
+    ocam = G.oracle_camera(cam, w, h)
+    ref = None
+    for kind in G.KERNELS:
+        frame = G.oracle_frame(oracle_mod, sc, ocam, kind, spec, ml["materials"], ml["lights"])
+        G.assert_frame(G.render(ctx, dev, cam, G.kernel(kind, dev, sh, spec), w, h), frame, kind, 8, where)
+        ref = frame if kind == "ao" else ref
+    # the side of the sphere's normal, from the oracle's hits: n = (pos - center) / radius, view = -dir
+    eye, cu, cv, cw = (np.float64(a) for a in ocam[:4])
+    y, x = np.divmod(np.arange(w * h), w)
+    d = cu[None] * (2.0 * (x + 0.5) / w - 1.0)[:, None] + cv[None] * (2.0 * (y + 0.5) / h - 1.0)[:, None] + cw[None]
+    d /= np.linalg.norm(d, axis=1)[:, None]
+    on_sphere = ref["prim_id"] == 1
+    n = (eye[None] + d * np.float64(ref["t"])[:, None]) / 0.7
+    facing = -(n * d).sum(axis=1)
+    assert (ref["prim_id"] == 0).any()
+    if where == "outside":
+        assert on_sphere.sum() > 30 and (facing[on_sphere] > 0.0).all() and ref["occ"][ref["prim_id"] == 0].any()
+    else:
+        assert np.linalg.norm(eye) < 0.7 and not on_sphere.any() and (facing[on_sphere] < 0.0).all()
 
 
 def test_tree_deeper_than_the_lds_stack_is_refused_and_leaves_the_target_untouched(ctx):
