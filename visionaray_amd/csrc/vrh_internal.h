@@ -47,6 +47,9 @@ constexpr uint32_t prim_record_bytes(uint32_t kind)
     return kind == VRH_PRIM_TRI64 ? 64u : kind == VRH_PRIM_SPHERE48 ? 48u : kind == VRH_PRIM_GENERIC80 ? 80u : 0u;
 }
 
+// bytes of one leaf-ordered device record of a primitive kind (a generic primitive takes the triangle's)
+constexpr uint32_t leaf_record_bytes(uint32_t kind) { return kind == VRH_PRIM_SPHERE48 ? 32u : 48u; }
+
 // Device flags word of a leaf-ordered primitive (vrh_device.h): bit 0 END_BIT, bit 1 the record is a sphere
 // (generic scenes only).
 constexpr uint32_t PRIM_FLAG_END = 1u, PRIM_FLAG_SPHERE = 2u;
@@ -99,6 +102,31 @@ struct fused_records
 };
 bool build_quads(const node32* nodes, uint32_t num_nodes, std::vector<float>& out, uint32_t& root_link,
                  uint32_t& quad_depth, fused_records* fz = nullptr, bool never_hit_unused = false);
+
+// The host half of vrh_scene_upload (vrh_upload.cpp): the caller's tree is validated and re-laid into exactly the
+// bytes the device arrays receive.  The options are those of the context and of the library the runtime is built
+// for: VRH_OPT_PAIR_LAYOUT, VRH_OPT_FUSED_WIDEN, whether the kernels walk fused records, and whether their 4-wide
+// step needs never-hit boxes in unused entries (build_quads).
+struct upload_options
+{
+    int pair_layout = 0, fused_widen = 0;
+    bool want_fused = false, never_hit_unused = false;
+};
+struct prepared_scene
+{
+    std::vector<float> pairs;                     // 16 floats per pair record, at least one record
+    std::vector<float> prims;                     // leaf-ordered records of leaf_record_bytes(kind)
+    std::vector<float> quads, fused_recs, leaf_boxes;     // empty where the scene has none
+    uint32_t root = 0, num_pairs = 0, num_indices = 0, max_depth = 0, quad_depth = 0, max_prim_id = 0, max_geom_id = 0;
+    float fused_omax = 0.0f;
+    bool finite_bounds = true, have_quads = false, fused_built = false;
+};
+// VRH_OK, or VRH_ERR_INVALID with the defect in `err` (`out` is then unspecified); `indices` may be null (identity)
+int prepare_scene(const void* nodes, uint32_t num_nodes, const void* prims, uint32_t num_prims, uint32_t kind,
+                  const uint32_t* indices, uint32_t num_indices, const upload_options& opt, prepared_scene& out,
+                  std::string& err);
+// every generic primitive holds a triangle or a sphere; false: the first other type index, in `err` under the name `who`
+bool check_generic_types(const void* prims, uint32_t num_prims, const char* who, std::string& err);
 
 int build_bvh(const void* prims, uint32_t n, uint32_t kind, node32* nodes_out, uint32_t* num_nodes_out,
               uint32_t* indices_out, uint32_t* max_depth_out);

@@ -41,6 +41,42 @@ int select_device(vrh_ctx* ctx)
     return VRH_OK;
 }
 
+// a scene under construction (vrh_scene_upload, vrh_scene_list_create, vrh_scene_build)
+vrh_scene* new_scene(vrh_ctx* ctx)
+{
+    auto* sc = new (std::nothrow) vrh_scene;
+    if (sc) sc->ctx = ctx;
+    else set_error("host allocation failed");
+    return sc;
+}
+
+// a HIP failure of entry point `who` at `what`: the scene and what it owns are freed
+int scene_fail(vrh_scene* sc, hipError_t e, const char* who, const char* what)
+{
+    set_error(std::string(who) + ": " + what + ": " + hipGetErrorString(e));
+    vrh_scene_free(sc);
+    return e == hipErrorOutOfMemory ? VRH_ERR_OOM : VRH_ERR_HIP;
+}
+
+// one host block into a device array of the scene, counted in `total`
+int scene_block(vrh_scene* sc, float4*& dst, const void* src, size_t bytes, uint64_t& total, const char* who, const char* what)
+{
+    hipError_t e = hipMalloc(&dst, bytes);
+    if (e == hipSuccess) e = hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) return scene_fail(sc, e, who, what);
+    total += bytes;
+    return VRH_OK;
+}
+
+// the fields of vrh_scene_info that every kind of scene has
+void scene_info(vrh_scene* sc, uint32_t bvhs, uint32_t nodes, uint32_t prims, uint32_t indices, uint32_t kind,
+                uint32_t depth, uint32_t max_prim_id, uint32_t max_geom_id, uint64_t device_bytes)
+{
+    sc->info.num_bvhs = bvhs; sc->info.num_nodes = nodes; sc->info.num_prims = prims; sc->info.num_indices = indices;
+    sc->info.prim_kind = kind; sc->info.max_depth = depth;
+    sc->info.max_prim_id = max_prim_id; sc->info.max_geom_id = max_geom_id; sc->info.device_bytes = device_bytes;
+}
+
 // a render group's root writes its target on the group's stream (vrh_render_sharded): work on the
 // target's context stream waits for that (an event wait, no host synchronisation)
 int rt_wait(vrh_ctx* ctx, vrh_rt* rt)
@@ -275,251 +311,39 @@ VRH_API int vrh_scene_upload(vrh_ctx* ctx, const void* nodes_v, uint32_t num_nod
 {
     VRH_CHECK(ctx && out && nodes_v && prims_v, "vrh_scene_upload: null argument");
     VRH_CHECK(num_nodes >= 1 && num_prims >= 1, "vrh_scene_upload: empty BVH");
-    VRH_CHECK(prim_record_bytes(prim_kind) != 0u, "vrh_scene_upload: unknown prim_kind");
-    if (prim_kind == VRH_PRIM_GENERIC80)
-        for (uint32_t i = 0; i < num_prims; ++i)
-        {
-            const uint32_t ty = static_cast<const generic80*>(prims_v)[i].type;
-            VRH_CHECK(ty == VRH_GENERIC_TYPE_TRI || ty == VRH_GENERIC_TYPE_SPHERE,
-                      "vrh_scene_upload: generic primitive " + std::to_string(i) + " has type index " + std::to_string(ty)
-                          + " (1 triangle, 2 sphere)");
-        }
-    VRH_CHECK(num_nodes % 2 == 1, "vrh_scene_upload: node count must be odd (root + child pairs)");
     *out = nullptr;
-    if (!indices) num_indices = num_prims;
-    auto nodes = static_cast<const node32*>(nodes_v);
-
-    // -- node pairs + topology validation + depth
-    const uint32_t npairs = (num_nodes - 1) / 2;
-    std::vector<float4> pairs(4 * std::max<uint32_t>(npairs, 1), make_float4(0, 0, 0, 0));
-    std::vector<uint8_t> end_flag(num_indices, 0);
-    auto link_of = [&](const node32& c, uint32_t& link) -> bool {
-        if (c.num_prims != 0)
-        {
-            if (uint64_t(c.first) + c.num_prims > num_indices || c.first >= 0x80000000u) return false;
-            end_flag[c.first + c.num_prims - 1] = 1;
-            link = 0x80000000u | c.first;
-            return true;
-        }
-        if (c.first == 0 || c.first % 2 != 1 || uint64_t(c.first) + 1 >= num_nodes) return false;
-        link = (c.first - 1) / 2;
-        return true;
-    };
-    uint32_t root = 0;
-    if (!link_of(nodes[0], root)) { set_error("vrh_scene_upload: malformed root node"); return VRH_ERR_INVALID; }
-    if (nodes[0].num_prims == 0 && nodes[0].first != 1) { set_error("vrh_scene_upload: root children must be nodes 1,2"); return VRH_ERR_INVALID; }
-    for (uint32_t k = 0; k < npairs; ++k)
+    // validation and the device layouts are host work (vrh_upload.cpp); what differs between the libraries built from
+    // this file goes in as options: fused records for a VRH_FUSED_STEP build, never-hit unused entries for the default
+    const upload_options opt{ ctx->opt.layout, ctx->opt_fused_widen, VRH_FUSED_STEP != 0 && ctx->opt_fused_step != 2,
+                              vrh::dev::NEVER_HIT_UNUSED };
+    prepared_scene p;
+    std::string err;
+    int rc = prepare_scene(nodes_v, num_nodes, prims_v, num_prims, prim_kind, indices, num_indices, opt, p, err);
+    if (rc) { set_error(err); return rc; }
+    if ((rc = select_device(ctx))) return rc;
+    vrh_scene* sc = new_scene(ctx);
+    if (!sc) return VRH_ERR_OOM;
+    sc->roots[0] = p.root;
+    sc->num_pairs = p.num_pairs;
+    sc->finite_bounds = p.finite_bounds;
+    const char* who = "vrh_scene_upload";
+    auto bytes_of = [](const std::vector<float>& v) { return v.size() * sizeof(float); };
+    uint64_t bytes = 0, fused_bytes = 0;       // the fused arrays are not part of device_bytes, which the launch plan reads
+    if ((rc = scene_block(sc, sc->pairs, p.pairs.data(), bytes_of(p.pairs), bytes, who, "pairs"))) return rc;
+    if ((rc = scene_block(sc, sc->prims, p.prims.data(), bytes_of(p.prims), bytes, who, "prims"))) return rc;
+    if (p.have_quads && (rc = scene_block(sc, sc->quads, p.quads.data(), bytes_of(p.quads), bytes, who, "quads"))) return rc;
+    if (p.fused_built)
     {
-        const node32& c0 = nodes[2 * k + 1];
-        const node32& c1 = nodes[2 * k + 2];
-        uint32_t l0, l1;
-        if (!link_of(c0, l0) || !link_of(c1, l1)) { set_error("vrh_scene_upload: malformed node pair " + std::to_string(k)); return VRH_ERR_INVALID; }
-        float4* q = &pairs[4 * k];
-        // slab-major, child-interleaved (vrh_device.h): packed (child 0, child 1) operand pairs
-        q[0] = make_float4(c0.bmin[0], c1.bmin[0], c0.bmin[1], c1.bmin[1]);
-        q[1] = make_float4(c0.bmin[2], c1.bmin[2], c0.bmax[0], c1.bmax[0]);
-        q[2] = make_float4(c0.bmax[1], c1.bmax[1], c0.bmax[2], c1.bmax[2]);
-        uint32_t w[4] = { l0, l1, 0u, 0u };
-        std::memcpy(&q[3], w, 16);
+        if ((rc = scene_block(sc, sc->fquads, p.fused_recs.data(), bytes_of(p.fused_recs), fused_bytes, who, "fused records"))) return rc;
+        if ((rc = scene_block(sc, sc->leaf_boxes, p.leaf_boxes.data(), bytes_of(p.leaf_boxes), fused_bytes, who, "leaf boxes"))) return rc;
+        sc->fused_omax = p.fused_omax;
+        sc->info.fused_records = uint32_t(p.quads.size() / 32);
+        sc->info.fused_bytes = fused_bytes;
     }
-    // depth (root depth 0) by iterative DFS over links
-    uint32_t max_depth = 0;
-    {
-        // every pair may be reached at most once: a pair reached twice (a DAG or a cycle) is rejected
-        std::vector<std::pair<uint32_t, uint32_t>> st;
-        std::vector<uint8_t> seen(npairs, 0);
-        if (!(root & 0x80000000u)) st.push_back({ root, 1u });
-        while (!st.empty())
-        {
-            auto e = st.back(); st.pop_back();
-            if (seen[e.first]) { set_error("vrh_scene_upload: BVH is not a tree (a node pair is reached twice)"); return VRH_ERR_INVALID; }
-            seen[e.first] = 1;
-            max_depth = std::max(max_depth, e.second);
-            uint32_t w[4];
-            std::memcpy(w, &pairs[4 * e.first + 3], 16);
-            for (int c = 0; c < 2; ++c)
-                if (!(w[c] & 0x80000000u))
-                {
-                    if (w[c] >= npairs) { set_error("vrh_scene_upload: child pair out of range"); return VRH_ERR_INVALID; }
-                    st.push_back({ w[c], e.second + 1 });
-                }
-        }
-    }
-
-    // -- cache-line pairing (VRH_OPT_PAIR_LAYOUT = 1; auto off: measured neutral, within 1.3 %,
-    // profiles/r01/ab_layout.log): re-lay the pair records in a depth-first
-    // preorder that puts each pair's child-0 pair right after it, so a parent and a child share a
-    // 128-B line on half of the descent steps (31 % in the builder's order).  Links are renumbered;
-    // the tree, the traversal order and every result are unchanged.
-    if (ctx->opt.layout == 1 && npairs > 1 && !(root & 0x80000000u))
-    {
-        std::vector<uint32_t> perm(npairs, 0xFFFFFFFFu);
-        uint32_t next = 0;
-        std::vector<uint32_t> st{ root };
-        while (!st.empty())
-        {
-            const uint32_t k = st.back(); st.pop_back();
-            perm[k] = next++;
-            uint32_t w[4];
-            std::memcpy(w, &pairs[4 * k + 3], 16);
-            if (!(w[1] & 0x80000000u)) st.push_back(w[1]);
-            if (!(w[0] & 0x80000000u)) st.push_back(w[0]);
-        }
-        for (uint32_t k = 0; k < npairs; ++k)
-            if (perm[k] == 0xFFFFFFFFu) perm[k] = next++;      // unreachable records keep a slot
-        if (next != npairs) { set_error("vrh_scene_upload: pair layout: not a permutation"); return VRH_ERR_INVALID; }
-        std::vector<float4> np(pairs.size());
-        for (uint32_t k = 0; k < npairs; ++k)
-        {
-            float4* d = &np[4 * size_t(perm[k])];
-            std::memcpy(d, &pairs[4 * size_t(k)], 64);
-            uint32_t w[4];
-            std::memcpy(w, &d[3], 16);
-            for (int c = 0; c < 2; ++c)
-                if (!(w[c] & 0x80000000u)) w[c] = perm[w[c]];
-            std::memcpy(&d[3], w, 16);
-        }
-        pairs.swap(np);
-        root = perm[root];
-    }
-
-    // -- leaf-ordered primitives with END flags
-    // (a generic primitive takes the triangle's three words whichever alternative it holds: vrh_internal.h
-    // generic_leaf_record)
-    const uint32_t f4_per = prim_kind == VRH_PRIM_SPHERE48 ? 2u : 3u;
-    std::vector<float4> lp(size_t(f4_per) * num_indices);
-    for (uint32_t i = 0; i < num_indices; ++i)
-    {
-        uint32_t src = indices ? indices[i] : i;
-        if (src >= num_prims) { set_error("vrh_scene_upload: index out of range"); return VRH_ERR_INVALID; }
-        uint32_t flags = end_flag[i] ? 1u : 0u;
-        float4* q = &lp[size_t(f4_per) * i];
-        if (prim_kind == VRH_PRIM_TRI64)
-        {
-            const tri64& t = static_cast<const tri64*>(prims_v)[src];
-            q[0] = make_float4(t.v1[0], t.v1[1], t.v1[2], t.e1[0]);
-            q[1] = make_float4(t.e1[1], t.e1[2], t.e2[0], t.e2[1]);
-            uint32_t w[4];
-            std::memcpy(&w[0], &t.e2[2], 4);
-            w[1] = t.prim_id; w[2] = t.geom_id; w[3] = flags;
-            std::memcpy(&q[2], w, 16);
-        }
-        else if (prim_kind == VRH_PRIM_GENERIC80)
-        {
-            uint32_t w[12];
-            generic_leaf_record(static_cast<const generic80*>(prims_v)[src], end_flag[i] != 0, w);   // types checked above
-            std::memcpy(q, w, 48);
-        }
-        else
-        {
-            const sphere48& s = static_cast<const sphere48*>(prims_v)[src];
-            q[0] = make_float4(s.center[0], s.center[1], s.center[2], s.radius);
-            uint32_t w[4] = { s.prim_id, s.geom_id, flags, 0u };
-            std::memcpy(&q[1], w, 16);
-        }
-    }
-
-    bool finite_bounds = true;
-    for (uint32_t i = 0; i < num_nodes && finite_bounds; ++i)
-        for (int a = 0; a < 3; ++a)
-            finite_bounds = finite_bounds && std::isfinite(nodes[i].bmin[a]) && std::isfinite(nodes[i].bmax[a]);
-
-    uint32_t max_prim_id = 0, max_geom_id = 0;
-    for (uint32_t i = 0; i < num_prims; ++i)
-    {
-        uint32_t ids[2];
-        std::memcpy(ids, static_cast<const uint8_t*>(prims_v) + size_t(i) * prim_record_bytes(prim_kind), 8);
-        max_geom_id = std::max(max_geom_id, ids[0]);
-        max_prim_id = std::max(max_prim_id, ids[1]);
-    }
-
-    std::vector<float> quads;
-    uint32_t quad_root = 0, quad_depth = 0;
-    // the fused records (vrh_fused_slab.h) serve ray origins within twice the root box's largest coordinate: an
-    // AO ray starts on a surface, inside the root box; a ray from farther out walks the binary records
-    // (only in a build whose kernels walk them, VRH_FUSED_STEP -- libvrh_fused.so; VRH_OPT_FUSED_STEP 2 leaves them out)
-    fused_records fz;
-    const bool want_fused = VRH_FUSED_STEP != 0 && ctx->opt_fused_step != 2;
-    if (finite_bounds)
-    {
-        float extent = 0.0f;
-        for (int a = 0; a < 3; ++a)
-        {
-            fz.omax = std::max(fz.omax, 2.0f * std::max(std::fabs(nodes[0].bmin[a]), std::fabs(nodes[0].bmax[a])));
-            extent = std::max(extent, nodes[0].bmax[a] - nodes[0].bmin[a]);
-        }
-        fz.omax = vrh::fused::omax_floor(fz.omax);
-        fz.extra = ctx->opt_fused_widen ? std::ldexp(extent, -ctx->opt_fused_widen) : 0.0f;
-        fz.num_indices = num_indices;
-    }
-    // NEVER_HIT_UNUSED: the AO kernel's step does not compare links with QUAD_NONE, so unused entries get never-hit boxes
-    const bool have_quads = finite_bounds && build_quads(nodes, num_nodes, quads, quad_root, quad_depth, want_fused ? &fz : nullptr,
-                                                         vrh::dev::NEVER_HIT_UNUSED);
-
-    int rc = select_device(ctx);
-    if (rc) return rc;
-    auto* sc = new (std::nothrow) vrh_scene;
-    if (!sc) { set_error("host allocation failed"); return VRH_ERR_OOM; }
-    sc->ctx = ctx;
-    sc->roots[0] = root;
-    sc->num_pairs = npairs;
-    sc->finite_bounds = finite_bounds;
-    auto fail = [&](hipError_t e, const char* what) {
-        set_error(std::string(what) + ": " + hipGetErrorString(e));
-        vrh_scene_free(sc);
-        return e == hipErrorOutOfMemory ? VRH_ERR_OOM : VRH_ERR_HIP;
-    };
-    hipError_t e;
-    if ((e = hipMalloc(&sc->pairs, pairs.size() * sizeof(float4))) != hipSuccess) return fail(e, "hipMalloc(pairs)");
-    if ((e = hipMalloc(&sc->prims, lp.size() * sizeof(float4))) != hipSuccess) return fail(e, "hipMalloc(prims)");
-    if ((e = hipMemcpy(sc->pairs, pairs.data(), pairs.size() * sizeof(float4), hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "upload pairs");
-    if ((e = hipMemcpy(sc->prims, lp.data(), lp.size() * sizeof(float4), hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "upload prims");
-    uint64_t bytes = pairs.size() * sizeof(float4) + lp.size() * sizeof(float4);
-    if (have_quads)
-    {
-        const size_t qb = quads.size() * sizeof(float);
-        if ((e = hipMalloc(&sc->quads, qb)) != hipSuccess) return fail(e, "hipMalloc(quads)");
-        if ((e = hipMemcpy(sc->quads, quads.data(), qb, hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "upload quads");
-        sc->quad_depth = quad_depth;
-        sc->info.wide_records = uint32_t(quads.size() / 32);
-        sc->info.wide_depth = quad_depth;
-        bytes += qb;
-        if (fz.built)
-        {
-            // the leaves' exact boxes, two float4 per leaf-ordered primitive (read at a leaf's first primitive)
-            std::vector<float> boxes(size_t(8) * fz.leaf_slot.size(), 0.0f);
-            for (size_t i = 0; i < fz.leaf_slot.size(); ++i)
-            {
-                const uint32_t s = fz.leaf_slot[i];
-                if (s == QUAD_NONE) continue;
-                const float* rec = &quads[size_t(s >> 2) * 32 + (s & 3u)];
-                for (int a = 0; a < 3; ++a) { boxes[8 * i + a] = rec[4 * a]; boxes[8 * i + 4 + a] = rec[12 + 4 * a]; }
-            }
-            const size_t sb = boxes.size() * sizeof(float);
-            if ((e = hipMalloc(&sc->fquads, qb)) != hipSuccess) return fail(e, "hipMalloc(fused records)");
-            if ((e = hipMemcpy(sc->fquads, fz.recs.data(), qb, hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "upload fused records");
-            if ((e = hipMalloc(&sc->leaf_boxes, sb)) != hipSuccess) return fail(e, "hipMalloc(leaf boxes)");
-            if ((e = hipMemcpy(sc->leaf_boxes, boxes.data(), sb, hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "upload leaf boxes");
-            sc->fused_omax = fz.omax;
-            sc->info.fused_records = sc->info.wide_records;
-            sc->info.fused_bytes = qb + sb;       // not part of device_bytes, which the launch plan reads
-        }
-    }
-    if (face_normals)
-    {
-        if ((e = hipMalloc(&sc->normals, size_t(num_prims) * sizeof(float4))) != hipSuccess) return fail(e, "hipMalloc(normals)");
-        if ((e = hipMemcpy(sc->normals, face_normals, size_t(num_prims) * sizeof(float4), hipMemcpyHostToDevice)) != hipSuccess) return fail(e, "upload normals");
-        bytes += size_t(num_prims) * sizeof(float4);
-    }
-    sc->info.num_nodes = num_nodes;
-    sc->info.num_bvhs = 1;
-    sc->info.num_prims = num_prims;
-    sc->info.num_indices = num_indices;
-    sc->info.prim_kind = prim_kind;
-    sc->info.max_depth = max_depth;
-    sc->info.max_prim_id = max_prim_id;
-    sc->info.max_geom_id = max_geom_id;
-    sc->info.device_bytes = bytes;
+    if (face_normals && (rc = scene_block(sc, sc->normals, face_normals, size_t(num_prims) * sizeof(float4), bytes, who, "normals"))) return rc;
+    sc->quad_depth = sc->info.wide_depth = p.quad_depth;
+    sc->info.wide_records = uint32_t(p.quads.size() / 32);
+    scene_info(sc, 1, num_nodes, num_prims, p.num_indices, prim_kind, p.max_depth, p.max_prim_id, p.max_geom_id, bytes);
     *out = sc;
     return VRH_OK;
 }
@@ -615,15 +439,10 @@ VRH_API int vrh_scene_list_create(vrh_ctx* ctx, const vrh_scene* const* scenes, 
     VRH_CHECK(!face_normals || uint64_t(num_normals) > max_pid, "vrh_scene_list_create: face normals must cover every prim_id");
     int rc = select_device(ctx);
     if (rc) return rc;
-    auto* sc = new (std::nothrow) vrh_scene;
-    if (!sc) { set_error("host allocation failed"); return VRH_ERR_OOM; }
-    sc->ctx = ctx;
-    auto fail = [&](hipError_t e, const char* what) {
-        set_error(std::string("vrh_scene_list_create: ") + what + ": " + hipGetErrorString(e));
-        vrh_scene_free(sc);
-        return e == hipErrorOutOfMemory ? VRH_ERR_OOM : VRH_ERR_HIP;
-    };
-    const uint32_t f4_per = kind == VRH_PRIM_TRI64 ? 3u : 2u;
+    vrh_scene* sc = new_scene(ctx);
+    if (!sc) return VRH_ERR_OOM;
+    auto fail = [&](hipError_t e, const char* what) { return scene_fail(sc, e, "vrh_scene_list_create", what); };
+    const uint32_t f4_per = leaf_record_bytes(kind) / 16;
     hipError_t e;
     if ((e = hipMalloc(&sc->pairs, std::max<uint64_t>(pairs, 1) * 64)) != hipSuccess) return fail(e, "pairs");
     if ((e = hipMalloc(&sc->prims, prims * f4_per * 16)) != hipSuccess) return fail(e, "prims");
@@ -658,15 +477,7 @@ VRH_API int vrh_scene_list_create(vrh_ctx* ctx, const vrh_scene* const* scenes, 
     sc->num_roots = count;
     sc->num_pairs = uint32_t(pairs);
     sc->finite_bounds = finite;
-    sc->info.num_nodes = uint32_t(nodes);
-    sc->info.num_prims = uint32_t(prims);
-    sc->info.num_indices = uint32_t(prims);
-    sc->info.prim_kind = kind;
-    sc->info.max_depth = depth;
-    sc->info.max_prim_id = max_pid;
-    sc->info.max_geom_id = max_gid;
-    sc->info.device_bytes = bytes;
-    sc->info.num_bvhs = count;
+    scene_info(sc, count, uint32_t(nodes), uint32_t(prims), uint32_t(prims), kind, depth, max_pid, max_gid, bytes);
     *out = sc;
     return VRH_OK;
 }
@@ -689,41 +500,22 @@ VRH_API int vrh_scene_build(vrh_ctx* ctx, const void* prims, uint32_t num_prims,
     std::string err;
     rc = build_lbvh(prims, num_prims, prim_kind, desc && desc->max_leaf ? desc->max_leaf : 4u, ctx->stream, b, err);
     if (rc) { set_error(err); return rc; }
-    auto* sc = new (std::nothrow) vrh_scene;
+    vrh_scene* sc = new_scene(ctx);
     if (!sc)
     {
         for (void* p : { (void*)b.nodes, (void*)b.indices, (void*)b.pairs, (void*)b.prims }) (void)hipFree(p);
-        set_error("host allocation failed");
         return VRH_ERR_OOM;
     }
-    sc->ctx = ctx;
     sc->pairs = b.pairs; sc->prims = b.prims; sc->dnodes = b.nodes; sc->dindices = b.indices;
     sc->roots[0] = b.root;
     sc->num_pairs = b.num_pairs;
     sc->finite_bounds = b.finite;
-    uint64_t bytes = uint64_t(std::max(b.num_pairs, 1u)) * 64 + uint64_t(num_prims) * (prim_kind == VRH_PRIM_TRI64 ? 48 : 32);
-    if (face_normals)
-    {
-        hipError_t e = hipMalloc(&sc->normals, size_t(num_prims) * sizeof(float4));
-        if (e == hipSuccess) e = hipMemcpy(sc->normals, face_normals, size_t(num_prims) * sizeof(float4), hipMemcpyHostToDevice);
-        if (e != hipSuccess)
-        {
-            set_error(std::string("vrh_scene_build: normals: ") + hipGetErrorString(e));
-            vrh_scene_free(sc);
-            return VRH_ERR_HIP;
-        }
-        bytes += uint64_t(num_prims) * sizeof(float4);
-    }
-    sc->info.num_nodes = b.num_nodes;
-    sc->info.num_prims = num_prims;
-    sc->info.num_indices = num_prims;
-    sc->info.prim_kind = prim_kind;
-    sc->info.max_depth = b.max_depth;
-    sc->info.device_bytes = bytes;
-    sc->info.max_prim_id = b.max_prim_id;
-    sc->info.max_geom_id = b.max_geom_id;
+    uint64_t bytes = uint64_t(std::max(b.num_pairs, 1u)) * 64 + uint64_t(num_prims) * leaf_record_bytes(prim_kind);
+    if (face_normals
+        && (rc = scene_block(sc, sc->normals, face_normals, size_t(num_prims) * sizeof(float4), bytes, "vrh_scene_build", "normals")))
+        return rc;
+    scene_info(sc, 1, b.num_nodes, num_prims, num_prims, prim_kind, b.max_depth, b.max_prim_id, b.max_geom_id, bytes);
     sc->info.gpu_built = 1;
-    sc->info.num_bvhs = 1;
     sc->info.build_ms = b.build_ms;
     *out = sc;
     return VRH_OK;
@@ -2050,14 +1842,8 @@ VRH_API int vrh_build_bvh(const void* prims, uint32_t num_prims, uint32_t kind, 
     VRH_CHECK(prims && nodes_out && num_nodes_out && indices_out, "vrh_build_bvh: null argument");
     VRH_CHECK(num_prims >= 1, "vrh_build_bvh: no primitives");
     VRH_CHECK(prim_record_bytes(kind) != 0u, "vrh_build_bvh: unknown prim kind");
-    if (kind == VRH_PRIM_GENERIC80)
-        for (uint32_t i = 0; i < num_prims; ++i)
-        {
-            const uint32_t ty = static_cast<const generic80*>(prims)[i].type;
-            VRH_CHECK(ty == VRH_GENERIC_TYPE_TRI || ty == VRH_GENERIC_TYPE_SPHERE,
-                      "vrh_build_bvh: generic primitive " + std::to_string(i) + " has type index " + std::to_string(ty)
-                          + " (1 triangle, 2 sphere)");
-        }
+    std::string err;
+    VRH_CHECK(kind != VRH_PRIM_GENERIC80 || check_generic_types(prims, num_prims, "vrh_build_bvh", err), err);
     try
     {
         return build_bvh(prims, num_prims, kind, static_cast<node32*>(nodes_out), num_nodes_out, indices_out, max_depth_out);
