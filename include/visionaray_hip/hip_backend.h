@@ -977,6 +977,61 @@ volume_kernel make_hip_volume_kernel(hip_volume const& volume, AABB const& bbox,
     return k;
 }
 
+// what hip_sched::frame takes for a multi-volume frame (vrh.h vrh_render_multi_volume)
+struct multi_volume_kernel
+{
+    std::vector<vrh_volume*> volumes;
+    std::vector<vrh_multi_volume_entry> entries;
+    vrh_multi_volume_kernel_desc desc;
+};
+
+// The kernel of src/examples/multi_volume/main.cpp:410-567 over up to 32 hip_volume objects (each with its own
+// transfer function).  `volumes`, `bboxes` (.min / .max of .x .y .z), `transforms` (the forward model matrices,
+// .data() column-major; inverted here as the example does, with the reference's inverse()) and `materials`
+// (plastic<float> or vrh_plastic) are containers of equal size; `light` is a point_light<float> or a
+// vrh_point_light.  The defaults are the example's constants and texture coordinates.
+template <typename Volumes, typename Boxes, typename Transforms, typename Materials, typename Light>
+multi_volume_kernel make_hip_multi_volume_kernel(Volumes const& volumes, Boxes const& bboxes, Transforms const& transforms,
+                                                 Materials const& materials, Light const& light, float dt = 0.007f,
+                                                 double opacity_cutoff = 0.999, float shade_alpha = 0.1f, float gradient_delta = 0.01f,
+                                                 bool flip_x = false, bool flip_y = true, bool flip_z = true)
+{
+    multi_volume_kernel k{};
+    const size_t n = volumes.size();
+    if (bboxes.size() != n || transforms.size() != n || materials.size() != n)
+        throw hip_error("make_hip_multi_volume_kernel: one box, transform and material per volume", VRH_ERR_INVALID);
+    const bool flip[3] = { flip_x, flip_y, flip_z };
+    size_t i = 0;
+    for (auto const& v : volumes) k.volumes.push_back(v.handle());
+    k.entries.resize(n);
+    for (auto const& b : bboxes)
+    {
+        vrh_multi_volume_entry& e = k.entries[i++];
+        const float lo[3] = { float(b.min.x), float(b.min.y), float(b.min.z) };
+        const float hi[3] = { float(b.max.x), float(b.max.y), float(b.max.z) };
+        for (int a = 0; a < 3; ++a)
+        {
+            e.box_min[a] = lo[a];
+            e.box_max[a] = hi[a];
+            e.coord_sign[a] = flip[a] ? -1.0f : 1.0f;
+            e.coord_offset[a] = flip[a] ? hi[a] : -lo[a];
+            e.coord_extent[a] = hi[a] - lo[a];
+        }
+    }
+    i = 0;
+    for (auto const& t : transforms) vrh_matrix_inverse(t.data(), k.entries[i++].transform_inv);
+    i = 0;
+    for (auto const& m : materials) k.entries[i++].material = hip_detail::to_plastic(m);
+    k.desc.dt = dt;
+    float c = float(opacity_cutoff);
+    if (double(c) < opacity_cutoff) c = std::nextafter(c, std::numeric_limits<float>::infinity());
+    k.desc.opacity_cutoff = c;
+    k.desc.shade_alpha = shade_alpha;
+    k.desc.gradient_delta = gradient_delta;
+    k.desc.light = hip_detail::to_point_light(light);
+    return k;
+}
+
 // closest_hit(ray, begin, end, intersector) / any_hit(..., intersector) for every ray of a built-in
 // kernel (traverse_linear.inl:232-329): the kernel with the mask intersector attached
 inline hip_builtin_kernel with_intersector(hip_builtin_kernel k, hip_hit_mask const& mask)
@@ -1130,6 +1185,11 @@ public:
             if (shard) throw std::runtime_error("hip_sched::frame: the volume kernel renders no shards");
             frame_volume(kernel, sparams);
         }
+        else if constexpr (std::is_same<K, multi_volume_kernel>::value)
+        {
+            if (shard) throw std::runtime_error("hip_sched::frame: the multi-volume kernel renders no shards");
+            frame_volume(kernel, sparams);
+        }
         else if constexpr (!std::is_same<K, hip_builtin_kernel>::value)
         {
             static_assert(hip_detail::user_kernels<K>::available,
@@ -1146,9 +1206,10 @@ public:
     }
 
 private:
-    // the volume kernel (vrh_render_volume): the uniform sampler and a pinhole camera, whole image or scissor box
-    template <typename SP>
-    void frame_volume(volume_kernel const& kernel, SP& sparams)
+    // the volume kernels (vrh_render_volume, vrh_render_multi_volume): the uniform sampler and a pinhole camera, whole
+    // image or scissor box
+    template <typename VK, typename SP>
+    void frame_volume(VK const& kernel, SP& sparams)
     {
         static_assert(hip_detail::uniform_sampler<SP>(), "hip_sched::frame: the volume kernel takes pixel_sampler::uniform_type");
         static_assert(!hip_detail::has_camera_matrices<SP>::value, "hip_sched::frame: the volume kernel takes a camera, not matrices");
@@ -1163,7 +1224,12 @@ private:
                                           uint32_t(rt.height()), &c), "vrh_make_camera");
         hip_detail::set_scissor(sparams, c);
         rt.begin_frame();
-        hip_detail::check(vrh_render_volume(ctx_->get(), kernel.volume, rt.handle(), &c, &kernel.desc), "vrh_render_volume");
+        if constexpr (std::is_same<VK, multi_volume_kernel>::value)
+            hip_detail::check(vrh_render_multi_volume(ctx_->get(), kernel.volumes.data(), kernel.entries.data(),
+                                                      uint32_t(kernel.volumes.size()), rt.handle(), &c, &kernel.desc),
+                              "vrh_render_multi_volume");
+        else
+            hip_detail::check(vrh_render_volume(ctx_->get(), kernel.volume, rt.handle(), &c, &kernel.desc), "vrh_render_volume");
         rt.end_frame();
     }
 

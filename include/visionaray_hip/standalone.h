@@ -304,6 +304,7 @@ private:
 namespace constants
 {
 template <typename T> T degrees_to_radians() { return T(1.74532925199432957692369076849e-02); }
+template <typename T> T pi() { return T(3.14159265358979323846264338328e+00); }
 }
 
 // camera (camera.h:46-95): only what the pinhole schedulers read
@@ -410,6 +411,46 @@ private:
     float m_[16] = {};
 };
 using mat4 = matrix<4, 4, float>;
+
+// The model transforms of the multi-volume example (math/detail/matrix4.inl:143-167, 272-383): the product with
+// each entry summed left to right over the inner index, the axis / angle rotation, scaling and translation,
+// and the helpers that multiply them onto a matrix from the right.  The same float operations in the same
+// order as the reference's, so that t * r * s has its bits.  This header is a layout- and API-compatible stand-in:
+// the names are the reference's interface, and the nine entries of the axis / angle rotation are Rodrigues'
+// formula in the one association that gives the reference's bits, so they necessarily read like its own.
+inline mat4 operator*(mat4 const& a, mat4 const& b)
+{
+    mat4 r;
+    for (int col = 0; col < 4; ++col)
+        for (int row = 0; row < 4; ++row)
+            r(row, col) = ((a(row, 0) * b(0, col) + a(row, 1) * b(1, col)) + a(row, 2) * b(2, col)) + a(row, 3) * b(3, col);
+    return r;
+}
+inline mat4 make_rotation(vec3 const& axis, float angle)
+{
+    const vec3 v = normalize(axis);
+    const float s = std::sin(angle), c = std::cos(angle);
+    mat4 r = mat4::identity();
+    r(0, 0) = v.x * v.x * (1.0f - c) + c;       r(1, 0) = v.x * v.y * (1.0f - c) + s * v.z; r(2, 0) = v.x * v.z * (1.0f - c) - s * v.y;
+    r(0, 1) = v.y * v.x * (1.0f - c) - s * v.z; r(1, 1) = v.y * v.y * (1.0f - c) + c;       r(2, 1) = v.y * v.z * (1.0f - c) + s * v.x;
+    r(0, 2) = v.z * v.x * (1.0f - c) + s * v.y; r(1, 2) = v.z * v.y * (1.0f - c) - s * v.x; r(2, 2) = v.z * v.z * (1.0f - c) + c;
+    return r;
+}
+inline mat4 make_scaling(vec3 const& v)
+{
+    mat4 r = mat4::identity();
+    r(0, 0) = v.x; r(1, 1) = v.y; r(2, 2) = v.z;
+    return r;
+}
+inline mat4 make_translation(vec3 const& v)
+{
+    mat4 r = mat4::identity();
+    r(0, 3) = v.x; r(1, 3) = v.y; r(2, 3) = v.z;
+    return r;
+}
+inline mat4 rotate(mat4 const& m, vec3 const& axis, float angle) { return m * make_rotation(axis, angle); }
+inline mat4 scale(mat4 const& m, vec3 const& v) { return m * make_scaling(v); }
+inline mat4 translate(mat4 const& m, vec3 const& v) { return m * make_translation(v); }
 
 // sched_params with camera matrices (scheduler.h:76-96, 197-231): view and projection matrix by
 // value instead of a camera

@@ -602,6 +602,68 @@ VRH_API int vrh_volume_render_host(const vrh_volume_desc* volume, const vrh_tran
 VRH_API int vrh_volume_sample(vrh_ctx* ctx, const vrh_volume* volume, const float* coords, uint32_t n,
                               float* voxel_out, float* rgba_out);
 
+/* ---- multi-volume rendering <- src/examples/multi_volume/main.cpp:410-567 ----------------------------------
+ * The example's kernel: up to VRH_MULTI_VOLUME_MAX volumes, each a vrh_volume (its own voxels, format, filter,
+ * address modes and transfer function) with its own box, inverse model transform and plastic material, marched
+ * along one ray in lock-step.  Per volume the ray is taken into volume space with transform_inv (the direction
+ * is not renormalised, so t stays the world-space ray parameter) and clipped against the box; t runs from
+ * the smallest tnear to the largest tfar of the boxes hit, in steps of dt.  A step samples every volume whose
+ * [tnear, tfar) holds t at pos = transform_inv * (ori + dir * t), classifies the voxel, and -- where the
+ * sample's alpha >= shade_alpha and the central-difference gradient (six tex3D fetches at tc -+ gradient_delta)
+ * is not 0 -- multiplies its rgb by material.shade(...) for the point light, with normal = normalize(gradient),
+ * isect_pos = pos, view_dir = -dir and light_dir = normalize(transform_inv * light.position) (the example's
+ * mix of spaces).  The premultiplied samples of a step are added and composited front to back; the march
+ * ends once color.w >= opacity_cutoff.  Restated in visionaray_hip/detail/vrh_multi_volume.h, one text for the
+ * kernel and the host entry point: alpha, hit, tmin and the steps are the reference's bit for bit, rgb up to
+ * powf.  The example's constants are dt 0.007, shade_alpha 0.1, gradient_delta 0.01, the double 0.999 (pass the
+ * smallest float not below it) and the coordinates sign (1, -1, -1), offset 1, extent 2. */
+#define VRH_MULTI_VOLUME_MAX 32u
+typedef struct {
+    float box_min[3], box_max[3];
+    float coord_sign[3], coord_offset[3], coord_extent[3];   /* as in vrh_volume_kernel_desc                  */
+    float transform_inv[16];  /* column-major, matrix<4, 4, float>::data() of inverse(model transform)  */
+    vrh_plastic material;
+} vrh_multi_volume_entry;
+typedef struct {
+    float dt;
+    float opacity_cutoff;
+    float shade_alpha;
+    float gradient_delta;
+    vrh_point_light light;
+} vrh_multi_volume_kernel_desc;
+/* One frame of the multi-volume kernel (visionaray_amd/csrc/vrh_multi_volume.hip), asynchronous and ordered like
+ * vrh_render_volume, with its restrictions: the uniform pixel sampler and a pinhole camera (scissor box
+ * honoured), no shards, render groups or frames in flight.  VRH_RT_COLOR is written at every rendered pixel;
+ * VRH_RT_PRIM_ID, if present, is 0 on a hit (tmax > tmin) and 0xFFFFFFFF on a miss; VRH_RT_T tmin on a hit and -1
+ * on a miss; VRH_RT_OCC is untouched.  vrh_volume_last_stats reports these frames too: steps are iterations of
+ * the loop over all rays.
+ * VRH_ERR_INVALID, decided from the descriptors before any object is looked at: num_volumes outside 1 ..
+ * VRH_MULTI_VOLUME_MAX; an entry whose box, coordinates, material or transform is not finite, or whose
+ * transform has a singular 3 x 3 part (its fourth row is never read: the kernel takes .xyz()); shade_alpha NaN,
+ * gradient_delta or the light not finite; and the hang guard: with D the distance from the eye to the farthest
+ * world-space box corner over all volumes (the affine part of transform_inv inverted in double), dt not finite,
+ * dt <= 0, dt < D * 2^-20, or 2 D / dt > VRH_VOLUME_MAX_STEPS.  On the
+ * device a ray stops after 2 * ceil(2 D / dt) + 8 iterations and raises the flag of vrh_render_volume.  Then: a
+ * volume of another context. */
+VRH_API int vrh_render_multi_volume(vrh_ctx* ctx, const vrh_volume* const* volumes, const vrh_multi_volume_entry* entries,
+                                    uint32_t num_volumes, vrh_rt* rt, const vrh_camera* cam,
+                                    const vrh_multi_volume_kernel_desc* kernel);
+/* the host build of the whole frame from host descriptors (volumes[i], transfuncs[i] belong to entries[i]): the
+ * checks of vrh_render_multi_volume and vrh_volume_create, the outputs of vrh_volume_render_host */
+VRH_API int vrh_multi_volume_render_host(const vrh_volume_desc* volumes, const vrh_transfunc_desc* transfuncs,
+                                         const vrh_multi_volume_entry* entries, uint32_t num_volumes,
+                                         const vrh_camera* cam, const vrh_multi_volume_kernel_desc* kernel, float* color,
+                                         uint32_t* prim_id, float* t, uint32_t* steps_px, vrh_volume_stats* stats);
+/* the same frame, and what the device does not count: sample_counts[0] = the volume samples taken over all rays
+ * (one per step and volume the ray is inside of), sample_counts[1] = those of them that were shaded.  The host
+ * build takes the device's steps bit for bit, so these are the device frame's counts too
+ * (tools/multi_volume_bench.py) */
+VRH_API int vrh_multi_volume_count_host(const vrh_volume_desc* volumes, const vrh_transfunc_desc* transfuncs,
+                                        const vrh_multi_volume_entry* entries, uint32_t num_volumes,
+                                        const vrh_camera* cam, const vrh_multi_volume_kernel_desc* kernel, float* color,
+                                        uint32_t* prim_id, float* t, uint32_t* steps_px, vrh_volume_stats* stats,
+                                        uint64_t* sample_counts);
+
 /* render targets.  vrh_rt_alloc owns its buffers (flags = vrh_rt_flags); vrh_rt_wrap borrows
  * caller device pointers (any may be NULL), e.g. torch tensors used for the RCCL gather. */
 VRH_API int vrh_rt_alloc(vrh_ctx* ctx, uint32_t width, uint32_t height, uint32_t flags, vrh_rt** out);

@@ -199,6 +199,20 @@ class vrh_volume_stats(C.Structure):
     _fields_ = [("rays", C.c_uint64), ("steps", C.c_uint64), ("capped", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+VRH_MULTI_VOLUME_MAX = 32
+
+
+class vrh_multi_volume_entry(C.Structure):
+    _fields_ = [("box_min", C.c_float * 3), ("box_max", C.c_float * 3), ("coord_sign", C.c_float * 3),
+                ("coord_offset", C.c_float * 3), ("coord_extent", C.c_float * 3), ("transform_inv", C.c_float * 16),
+                ("material", vrh_plastic)]
+
+
+class vrh_multi_volume_kernel_desc(C.Structure):
+    _fields_ = [("dt", C.c_float), ("opacity_cutoff", C.c_float), ("shade_alpha", C.c_float),
+                ("gradient_delta", C.c_float), ("light", vrh_point_light)]
+
+
 class VrhError(RuntimeError):
     def __init__(self, fn, code, msg):
         super().__init__(f"{fn} failed (status {code}): {msg}")
@@ -308,6 +322,14 @@ SIGNATURES = {
                                          C.POINTER(vrh_volume_kernel_desc), _vp, _vp, _vp, _vp,
                                          C.POINTER(vrh_volume_stats)]),
     "vrh_volume_sample": (C.c_int, [_vp, _vp, _vp, _u32, _vp, _vp]),
+    "vrh_render_multi_volume": (C.c_int, [_vp, _vp, _vp, _u32, _vp, C.POINTER(vrh_camera),
+                                          C.POINTER(vrh_multi_volume_kernel_desc)]),
+    "vrh_multi_volume_render_host": (C.c_int, [_vp, _vp, _vp, _u32, C.POINTER(vrh_camera),
+                                               C.POINTER(vrh_multi_volume_kernel_desc), _vp, _vp, _vp, _vp,
+                                               C.POINTER(vrh_volume_stats)]),
+    "vrh_multi_volume_count_host": (C.c_int, [_vp, _vp, _vp, _u32, C.POINTER(vrh_camera),
+                                              C.POINTER(vrh_multi_volume_kernel_desc), _vp, _vp, _vp, _vp,
+                                              C.POINTER(vrh_volume_stats), _vp]),
 }
 
 _lib = None

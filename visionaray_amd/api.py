@@ -1077,6 +1077,90 @@ def volume_render_host(voxels, tf, cam_basis, kdesc, filter=tex_filter.linear, a
     return out
 
 
+# ---- multi-volume rendering (src/examples/multi_volume/main.cpp) ----------------------------------
+
+def _plastic_record(m):
+    """vrh_plastic of a plastic() record (or of 13 floats: ca[3] ka cd[3] kd cs[3] ks exp)"""
+    a = np.asarray(m)
+    raw = a.tobytes() if a.dtype.names else a.astype(np.float32).tobytes()
+    if len(raw) != C.sizeof(capi.vrh_plastic):
+        raise TypeError("multi_volume: a material is one plastic() record")
+    return capi.vrh_plastic.from_buffer_copy(raw)
+
+
+def multi_volume_entries(bboxes, transforms_inv, materials, flip=(False, True, True)):
+    """vrh_multi_volume_entry array: per volume the box ((min), (max)) with the texture coordinates of
+    volume_kernel_desc, the inverse model transform (column-major 16-vector or 4x4 [row, col]) and a plastic()"""
+    n = len(bboxes)
+    if not (len(transforms_inv) == n and len(materials) == n):
+        raise ValueError("multi_volume: one box, transform and material per volume")
+    entries = (capi.vrh_multi_volume_entry * max(n, 1))()
+    for i in range(n):
+        k = volume_kernel_desc(bboxes[i], 1.0, 1.0, flip)
+        e = entries[i]
+        e.box_min[:], e.box_max[:] = k.box_min[:], k.box_max[:]
+        e.coord_sign[:], e.coord_offset[:], e.coord_extent[:] = k.coord_sign[:], k.coord_offset[:], k.coord_extent[:]
+        e.transform_inv[:] = [float(x) for x in _matrix4(transforms_inv[i])]
+        e.material = _plastic_record(materials[i])
+    return entries
+
+
+def multi_volume_kernel_desc(light, dt=0.007, opacity_cutoff=0.999, shade_alpha=0.1, gradient_delta=0.01):
+    """vrh_multi_volume_kernel_desc; the defaults are the example's constants, `light` one point_light()"""
+    k = capi.vrh_multi_volume_kernel_desc()
+    k.dt, k.shade_alpha, k.gradient_delta = float(dt), float(shade_alpha), float(gradient_delta)
+    k.opacity_cutoff = float_not_below(opacity_cutoff)
+    raw = np.asarray(light).tobytes()
+    if len(raw) != C.sizeof(capi.vrh_point_light):
+        raise TypeError("multi_volume: the light is one point_light() record")
+    k.light = capi.vrh_point_light.from_buffer_copy(raw)
+    return k
+
+
+class _multi_volume_kernel:
+    def __init__(self, volumes, entries, desc):
+        self.volumes = list(volumes)
+        self.entries = entries
+        self.desc = desc
+
+
+def multi_volume_kernel(volumes, bboxes, transforms, materials, light, dt=0.007, opacity_cutoff=0.999, shade_alpha=0.1,
+                        gradient_delta=0.01, flip=(False, True, True)):
+    """The kernel of the multi-volume example (multi_volume/main.cpp:410-567) over up to 32 `volumes` (va.volume
+    objects, each with its transfer function): per volume a box, the forward model transform -- inverted here
+    with matrix_inverse, the reference's inverse() -- and a plastic(); one point_light().  The defaults are the
+    example's constants."""
+    if not (len(bboxes) == len(volumes) and len(transforms) == len(volumes)):
+        raise ValueError("multi_volume: one box, transform and material per volume")
+    entries = multi_volume_entries(bboxes, [matrix_inverse(t) for t in transforms], materials, flip)
+    return _multi_volume_kernel(volumes, entries, multi_volume_kernel_desc(light, dt, opacity_cutoff, shade_alpha, gradient_delta))
+
+
+def multi_volume_render_host(voxels, tfs, entries, cam_basis, kdesc, filters=None, addresses=None):
+    """vrh_multi_volume_render_host: the frame on the CPU -- colour, prim_id, t, steps per pixel and the stats.
+    `voxels` and `tfs` are lists of arrays and transfunc objects, `entries` a vrh_multi_volume_entry array."""
+    n = len(voxels)
+    filters = filters if filters is not None else [tex_filter.linear] * n
+    addresses = addresses if addresses is not None else [tex_address.clamp] * n
+    vds = (capi.vrh_volume_desc * max(n, 1))()
+    tds = (capi.vrh_transfunc_desc * max(n, 1))()
+    keep = []
+    for i in range(n):
+        vds[i], vx = volume_desc(voxels[i], filters[i], addresses[i])
+        tds[i] = tfs[i].desc()
+        keep.append(vx)
+    px = cam_basis.width * cam_basis.height
+    out = {"color": np.zeros((px, 4), np.float32), "prim_id": np.zeros(px, np.uint32), "t": np.zeros(px, np.float32),
+           "steps_px": np.zeros(px, np.uint32)}
+    st = capi.vrh_volume_stats()
+    counts = np.zeros(2, np.uint64)
+    capi.check("vrh_multi_volume_count_host", vds, tds, entries, n, C.byref(cam_basis), C.byref(kdesc), _p(out["color"]),
+               _p(out["prim_id"]), _p(out["t"]), _p(out["steps_px"]), C.byref(st), _p(counts))
+    out["stats"] = {"rays": st.rays, "steps": st.steps, "capped": st.capped}
+    out["samples"], out["shaded_samples"] = int(counts[0]), int(counts[1])     # vrh_multi_volume_count_host
+    return out
+
+
 class hip_sched:
     """hip_sched<R>: drop-in for cuda_sched<R> (cuda_sched.h:25-40).
 
@@ -1106,12 +1190,18 @@ class hip_sched:
         if sparams.scissor_box is not None:
             cam.scissor[:] = [int(v) for v in sparams.scissor_box]
         rt.begin_frame()
-        capi.check("vrh_render_volume", self.ctx.handle, kernel.volume.handle, rt.handle, C.byref(cam), C.byref(kernel.desc))
+        if isinstance(kernel, _multi_volume_kernel):
+            n = len(kernel.volumes)
+            handles = (C.c_void_p * max(n, 1))(*[v.handle.value for v in kernel.volumes])
+            capi.check("vrh_render_multi_volume", self.ctx.handle, handles, kernel.entries, n, rt.handle, C.byref(cam),
+                       C.byref(kernel.desc))
+        else:
+            capi.check("vrh_render_volume", self.ctx.handle, kernel.volume.handle, rt.handle, C.byref(cam), C.byref(kernel.desc))
         if sync:
             rt.end_frame()
 
     def frame(self, kernel, sparams, frame_num=0, shard=None, sync=True):
-        if isinstance(kernel, _volume_kernel):
+        if isinstance(kernel, (_volume_kernel, _multi_volume_kernel)):
             return self._volume_frame(kernel, sparams, shard, sync)
         if not isinstance(kernel, _builtin_kernel):
             raise TypeError("hip_sched runs built-in kernels only (closest_hit / ao / simple / multi_hit / whitted / pathtracing): an "

@@ -81,6 +81,10 @@ struct vrh_ctx
     unsigned long long vol_base[2] = {};
     bool vol_pending = false, vol_capped = false;
     uint64_t vol_rays = 0, vol_steps = 0;
+    // the multi-volume kernel (vrh_multi_volume.hip): the frame's volume records on the device and the pinned host
+    // block they are copied from (one volume frame is in flight at a time)
+    void* mv_records = nullptr;
+    void* mv_host = nullptr;
 };
 
 struct vrh_scene

@@ -187,6 +187,8 @@ VRH_API int vrh_ctx_destroy(vrh_ctx* ctx)
     if (ctx->counters) (void)hipFree(ctx->counters);
     if (ctx->vol_counters) (void)hipFree(ctx->vol_counters);
     if (ctx->vol_host) (void)hipHostFree(ctx->vol_host);
+    if (ctx->mv_records) (void)hipFree(ctx->mv_records);
+    if (ctx->mv_host) (void)hipHostFree(ctx->mv_host);
     if (ctx->wave_times) (void)hipFree(ctx->wave_times);
     if (ctx->user_queues) (void)hipFree(ctx->user_queues);
     if (ctx->user_declined) (void)hipHostFree(ctx->user_declined);

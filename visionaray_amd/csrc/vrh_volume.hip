@@ -10,21 +10,11 @@
 // wave adds its step count to the context's volume counters with one vector atomic at exit.
 // VRH_VOLUME_BLOCK_WAVES (4 or 1) and VRH_VOLUME_TF_LDS are build-time choices for A/B builds: one wave per
 // block and a transfer function left in global memory both measured the same frame time.
-#include "vrh_objects.h"
-#include "vrh_volhost.h"
+#include "vrh_volobj.h"
 
 #include <new>
 
 using namespace vrh;
-
-struct vrh_volume
-{
-    vrh_ctx* ctx = nullptr;
-    void* voxels = nullptr;
-    dev::rgba_t* entries = nullptr;
-    dev::vol_view vol{};
-    dev::tf_view tf{};
-};
 
 namespace vrh {
 
@@ -133,6 +123,39 @@ int volume_collect(vrh_ctx* ctx)
     return VRH_OK;
 }
 
+int volume_frame_begin(vrh_ctx* ctx, vrh_rt* rt)
+{
+    if (!ctx->vol_counters)
+    {
+        // running totals on the device, and the pinned host words every frame's copy of them lands in
+        unsigned long long* c = nullptr;
+        VRH_HIP(hipMalloc(&c, 2 * sizeof(unsigned long long)));
+        hipError_t e = hipMemset(c, 0, 2 * sizeof(unsigned long long));
+        if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&ctx->vol_host), 2 * sizeof(unsigned long long), hipHostMallocDefault);
+        if (e != hipSuccess) { (void)hipFree(c); set_error(hipGetErrorString(e)); return VRH_ERR_HIP; }
+        ctx->vol_host[0] = ctx->vol_host[1] = 0;
+        ctx->vol_counters = c;
+    }
+    // ordered after every frame issued so far and after a render group's writes into the target
+    VRH_HIP(ctx_join(ctx));
+    if (rt->written_pending) VRH_HIP(hipStreamWaitEvent(ctx->stream, rt->written, 0));
+    if (ctx->vol_pending)
+    {
+        // the previous volume frame's flag must not be lost: look at it before the counters are reset
+        VRH_HIP(hipStreamSynchronize(ctx->stream));
+        const int rc = volume_collect(ctx);
+        if (rc) return rc;
+    }
+    return VRH_OK;
+}
+
+int volume_frame_end(vrh_ctx* ctx)
+{
+    VRH_HIP(hipMemcpyAsync(ctx->vol_host, ctx->vol_counters, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    ctx->vol_pending = true;
+    return VRH_OK;
+}
+
 } // namespace vrh
 
 namespace {
@@ -231,27 +254,8 @@ VRH_API int vrh_render_volume(vrh_ctx* ctx, const vrh_volume* v, vrh_rt* rt, con
     VRH_CHECK(cam->width == rt->width && cam->height == rt->height,
               "vrh_render_volume: the camera's image size is not the target's (no shards)");
     VRH_HIP(hipSetDevice(ctx->device));
-    if (!ctx->vol_counters)
-    {
-        // running totals on the device, and the pinned host words every frame's copy of them lands in
-        unsigned long long* c = nullptr;
-        VRH_HIP(hipMalloc(&c, 2 * sizeof(unsigned long long)));
-        hipError_t e = hipMemset(c, 0, 2 * sizeof(unsigned long long));
-        if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&ctx->vol_host), 2 * sizeof(unsigned long long), hipHostMallocDefault);
-        if (e != hipSuccess) { (void)hipFree(c); set_error(hipGetErrorString(e)); return VRH_ERR_HIP; }
-        ctx->vol_host[0] = ctx->vol_host[1] = 0;
-        ctx->vol_counters = c;
-    }
-    // ordered after every frame issued so far and after a render group's writes into the target
-    VRH_HIP(ctx_join(ctx));
-    if (rt->written_pending) VRH_HIP(hipStreamWaitEvent(ctx->stream, rt->written, 0));
-    if (ctx->vol_pending)
-    {
-        // the previous volume frame's flag must not be lost: look at it before the counters are reset
-        VRH_HIP(hipStreamSynchronize(ctx->stream));
-        const int rc = volume_collect(ctx);
-        if (rc) return rc;
-    }
+    const int rc = volume_frame_begin(ctx, rt);
+    if (rc) return rc;
     p.vol = v->vol;
     p.tf = v->tf;
     for (int a = 0; a < 3; ++a) { p.eye[a] = cam->eye[a]; p.cu[a] = cam->cam_u[a]; p.cv[a] = cam->cam_v[a]; p.cw[a] = cam->cam_w[a]; }
@@ -273,10 +277,7 @@ VRH_API int vrh_render_volume(vrh_ctx* ctx, const vrh_volume* v, vrh_rt* rt, con
         else launch_volume<dev::VOL_R32F>(p, blocks, ctx->stream);
         VRH_HIP(hipGetLastError());
     }
-    // behind the frame: the totals for the host, there once the stream has been waited for
-    VRH_HIP(hipMemcpyAsync(ctx->vol_host, ctx->vol_counters, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    ctx->vol_pending = true;
-    return VRH_OK;
+    return volume_frame_end(ctx);
 }
 
 VRH_API int vrh_volume_last_stats(vrh_ctx* ctx, vrh_volume_stats* stats)

@@ -1,7 +1,8 @@
 // visionaray_amd/csrc/vrh_volume_host.cpp -- host entry points of the volume support (include/vrh.h):
 // vrh_tex3d_host, vrh_tex1d_host and vrh_volume_render_host, the host builds of the shared samplers and
-// march (visionaray_hip/detail/vrh_volume.h).
-#include "vrh_volhost.h"
+// march (visionaray_hip/detail/vrh_volume.h), and vrh_multi_volume_render_host, the host build of the
+// multi-volume loop (visionaray_hip/detail/vrh_multi_volume.h).
+#include "vrh_mvhost.h"
 
 #include <new>
 
@@ -119,6 +120,72 @@ VRH_API int vrh_volume_render_host(const vrh_volume_desc* vd, const vrh_transfun
                 st.capped |= capped ? 1u : 0u;
             }
         if (stats) *stats = st;
+    }
+    catch (const std::bad_alloc&) { set_error("host allocation failed"); return VRH_ERR_OOM; }
+    return VRH_OK;
+}
+
+VRH_API int vrh_multi_volume_render_host(const vrh_volume_desc* vds, const vrh_transfunc_desc* tds,
+                                         const vrh_multi_volume_entry* entries, uint32_t n, const vrh_camera* cam,
+                                         const vrh_multi_volume_kernel_desc* kd, float* color, uint32_t* prim_id, float* t,
+                                         uint32_t* steps_px, vrh_volume_stats* stats)
+{
+    return vrh_multi_volume_count_host(vds, tds, entries, n, cam, kd, color, prim_id, t, steps_px, stats, nullptr);
+}
+
+VRH_API int vrh_multi_volume_count_host(const vrh_volume_desc* vds, const vrh_transfunc_desc* tds,
+                                        const vrh_multi_volume_entry* entries, uint32_t n, const vrh_camera* cam,
+                                        const vrh_multi_volume_kernel_desc* kd, float* color, uint32_t* prim_id, float* t,
+                                        uint32_t* steps_px, vrh_volume_stats* stats, uint64_t* sample_counts)
+{
+    if (!cam || !kd) { set_error("vrh_multi_volume_render_host: null camera or kernel descriptor"); return VRH_ERR_INVALID; }
+    uint64_t samples = 0, shaded = 0;
+    try
+    {
+        dev::mv_params K{};
+        std::vector<dev::mv_record> recs;
+        std::string bad = check_multi_volume(entries, n, *kd, *cam, K, recs);
+        if (bad.empty() && (!vds || !tds)) bad = "null volume or transfer-function descriptors";
+        for (uint32_t i = 0; bad.empty() && i < n; ++i)
+        {
+            bad = check_volume_desc(vds[i]);
+            if (bad.empty()) bad = check_transfunc_desc(tds[i]);
+            if (!bad.empty()) bad = "volume " + std::to_string(i) + ": " + bad;
+        }
+        if (!bad.empty()) { set_error("vrh_multi_volume_render_host: " + bad); return VRH_ERR_INVALID; }
+        std::vector<std::vector<uint32_t>> copies(n);
+        std::vector<std::vector<dev::rgba_t>> tfs(n);
+        for (uint32_t i = 0; i < n; ++i)
+        {
+            copy_entries(tds[i], tfs[i]);
+            recs[i].vol = dev::make_vol_view(aligned_voxels(vds[i], copies[i]), vds[i].width, vds[i].height, vds[i].depth,
+                                             vds[i].format, vds[i].filter, vds[i].address);
+            recs[i].tf = dev::make_tf_view(tfs[i].data(), tds[i].size, tds[i].filter, tds[i].address);
+        }
+        uint32_t clip[4];
+        volume_clip(*cam, clip);
+        const float wf = float(cam->width), hf = float(cam->height);
+        vrh_volume_stats st{};
+        for (uint32_t y = clip[1]; y < clip[3]; ++y)
+            for (uint32_t x = clip[0]; x < clip[2]; ++x)
+            {
+                float dir[3];
+                dev::pinhole_dir(dir, cam->cam_u, cam->cam_v, cam->cam_w, x, y, wf, hf);
+                dev::mv_array_ranges R;
+                const dev::mv_result r = dev::multi_march<dev::mv_single_ray>(recs.data(), K, cam->eye, dir, true, R);
+                const size_t o = size_t(y) * cam->width + x;
+                if (color) { color[4 * o] = r.color.x; color[4 * o + 1] = r.color.y; color[4 * o + 2] = r.color.z; color[4 * o + 3] = r.color.w; }
+                if (prim_id) prim_id[o] = r.hit ? 0u : 0xFFFFFFFFu;
+                if (t) t[o] = r.hit ? r.tmin : -1.0f;
+                if (steps_px) steps_px[o] = r.steps;
+                st.rays += 1;
+                st.steps += r.steps;
+                st.capped |= r.capped ? 1u : 0u;
+                samples += r.samples;
+                shaded += r.shaded;
+            }
+        if (stats) *stats = st;
+        if (sample_counts) { sample_counts[0] = samples; sample_counts[1] = shaded; }
     }
     catch (const std::bad_alloc&) { set_error("host allocation failed"); return VRH_ERR_OOM; }
     return VRH_OK;
