@@ -399,7 +399,10 @@ VRH_API int vrh_ctx_set_option(vrh_ctx* ctx, uint32_t option, int64_t value);
 
 /* scene upload: copies the host arrays (reference layouts) into device memory the scene owns.
  * indices may be NULL for a non-index BVH (prims already in leaf order).  face_normals (vec3,
- * 16-B stride, indexed by prim_id) is required for VRH_KERNEL_AO on triangles. */
+ * 16-B stride, indexed by prim_id) is required for VRH_KERNEL_AO on triangles: num_prims rows are
+ * copied, so with face_normals every prim_id must be < num_prims (else VRH_ERR_INVALID, before any
+ * device call; primitives with larger ids upload without normals, e.g. as members of a scene list,
+ * whose normals vrh_scene_list_create takes). */
 VRH_API int vrh_scene_upload(vrh_ctx* ctx, const void* nodes, uint32_t num_nodes,
                              const void* prims, uint32_t num_prims, uint32_t prim_kind,
                              const uint32_t* indices, uint32_t num_indices,
@@ -894,7 +897,9 @@ VRH_API int vrh_unshard_host(const void* gathered, const vrh_wire_layout* wire, 
 /* GPU BVH construction: a linear BVH (Morton order, Karras 2012 hierarchy,
  * leaves of up to max_leaf primitives) built on the device straight into a scene -- no host build,
  * no host re-layout.  The tree differs from build<index_bvh<P>> (binned SAH), so closest-hit ties
- * on shared edges can resolve to another primitive; vrh_bvh_sah_cost measures its quality. */
+ * on shared edges can resolve to another primitive; vrh_bvh_sah_cost measures its quality.
+ * face_normals as for vrh_scene_upload: num_prims rows indexed by prim_id, so with face_normals
+ * every prim_id must be < num_prims (else VRH_ERR_INVALID, before any device call). */
 enum vrh_build_method { VRH_BUILD_LBVH = 0 };
 typedef struct {
     uint32_t method;          /* vrh_build_method                                               */
@@ -903,8 +908,9 @@ typedef struct {
 VRH_API int vrh_scene_build(vrh_ctx* ctx, const void* prims, uint32_t num_prims, uint32_t prim_kind,
                             const void* face_normals, const vrh_build_desc* desc, vrh_scene** out);
 /* the scene's tree in the reference layout (bvh_node, index array): nodes_out holds *num_nodes
- * entries on input (NULL: only query the count), indices_out num_prims entries.  Works for
- * uploaded and GPU-built scenes alike. */
+ * entries on input (NULL: only query the count), indices_out num_prims entries.  Only scenes
+ * built by vrh_scene_build keep their tree on the device: an uploaded scene (whose tree the
+ * caller holds) or a scene list is VRH_ERR_UNSUPPORTED. */
 VRH_API int vrh_scene_download_bvh(vrh_ctx* ctx, const vrh_scene* scene, void* nodes_out, uint32_t* num_nodes,
                                    uint32_t* indices_out);
 /* sah_cost (detail/bvh/statistics.h:30-73): ci * sum A(inner) / A(root) + cl * sum A(leaf) / A(root)

@@ -10,6 +10,7 @@ The tree is not the reference's binned-SAH tree, so the bar is:
     pixels (differences only where box rounding or equal-t ties differ between trees).
 """
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -17,39 +18,11 @@ import pytest
 import visionaray_amd as va
 from visionaray_amd import scenes
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from lbvh_ref import check_structure  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-def prim_bounds(prims):
-    if prims.dtype == va.TRIANGLE_DTYPE:
-        v1 = prims["v1"][:, :3]
-        a, b, c = v1, v1 + prims["e1"][:, :3], v1 + prims["e2"][:, :3]
-        return np.minimum(np.minimum(a, b), c), np.maximum(np.maximum(a, b), c)
-    c, r = prims["center"][:, :3], prims["radius"][:, None]
-    return c - r, c + r
-
-
-def check_structure(nodes, idx, prims, max_leaf):
-    n = len(prims)
-    assert np.array_equal(np.sort(idx), np.arange(n, dtype=np.uint32))
-    lo, hi = prim_bounds(prims)
-    bmin, bmax = nodes["bbox_min"], nodes["bbox_max"]
-    leaf = nodes["num_prims"] != 0
-    assert (nodes["num_prims"][leaf] <= max_leaf).all()
-    covered = np.zeros(n, np.int64)
-    for k in np.nonzero(leaf)[0]:
-        f, c = nodes["first"][k], nodes["num_prims"][k]
-        sel = idx[f:f + c]
-        covered[f:f + c] += 1
-        assert np.array_equal(bmin[k], lo[sel].min(0)) and np.array_equal(bmax[k], hi[sel].max(0))
-    assert (covered == 1).all()
-    inner = np.nonzero(~leaf)[0]
-    fc = nodes["first"][inner]
-    assert (fc % 2 == 1).all() and (fc + 1 < len(nodes)).all()
-    assert np.array_equal(bmin[inner], np.minimum(bmin[fc], bmin[fc + 1]))
-    assert np.array_equal(bmax[inner], np.maximum(bmax[fc], bmax[fc + 1]))
-    assert len(np.unique(fc)) == len(fc) and len(nodes) == 2 * len(inner) + 1
 
 
 @pytest.mark.parametrize("name,W,H", [("cornell12", 128, 128), ("hf64", 160, 90), ("hf200", 320, 180),

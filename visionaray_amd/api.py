@@ -313,6 +313,8 @@ class hip_index_bvh:
         prims = np.ascontiguousarray(prims)
         kind = _kind_of(prims)
         nrm = None if normals is None else np.ascontiguousarray(normals, np.float32)
+        if nrm is not None and nrm.shape != (len(prims), 4):
+            raise ValueError("normals must be (num_prims, 4) float32")
         h = C.c_void_p()
         desc = capi.vrh_build_desc(capi.VRH_BUILD_LBVH, max_leaf)
         capi.check("vrh_scene_build", ctx.handle, _p(prims), len(prims), kind, _p(nrm), C.byref(desc), C.byref(h))

@@ -322,6 +322,10 @@ VRH_API int vrh_scene_upload(vrh_ctx* ctx, const void* nodes_v, uint32_t num_nod
     std::string err;
     int rc = prepare_scene(nodes_v, num_nodes, prims_v, num_prims, prim_kind, indices, num_indices, opt, p, err);
     if (rc) { set_error(err); return rc; }
+    // the kernels read face_normals[prim_id], and num_prims rows are copied
+    VRH_CHECK(!face_normals || p.max_prim_id < num_prims,
+              "vrh_scene_upload: face normals are indexed by prim_id, but prim_id " + std::to_string(p.max_prim_id)
+                  + " is not below num_prims " + std::to_string(num_prims));
     if ((rc = select_device(ctx))) return rc;
     vrh_scene* sc = new_scene(ctx);
     if (!sc) return VRH_ERR_OOM;
@@ -496,6 +500,19 @@ VRH_API int vrh_scene_build(vrh_ctx* ctx, const void* prims, uint32_t num_prims,
     VRH_CHECK(prim_kind == VRH_PRIM_TRI64 || prim_kind == VRH_PRIM_SPHERE48, "vrh_scene_build: unknown prim_kind");
     VRH_CHECK(!desc || desc->method == VRH_BUILD_LBVH, "vrh_scene_build: unknown build method");
     *out = nullptr;
+    if (face_normals)
+    {
+        // the kernels read face_normals[prim_id], and num_prims rows are copied: checked before anything is built
+        const size_t stride = prim_kind == VRH_PRIM_TRI64 ? 64u : 48u;
+        for (uint32_t i = 0; i < num_prims; ++i)
+        {
+            uint32_t pid;
+            std::memcpy(&pid, static_cast<const char*>(prims) + i * stride + 4, 4);
+            VRH_CHECK(pid < num_prims, "vrh_scene_build: face normals are indexed by prim_id, but prim_id " + std::to_string(pid)
+                                           + " (primitive " + std::to_string(i) + ") is not below num_prims "
+                                           + std::to_string(num_prims));
+        }
+    }
     int rc = select_device(ctx);
     if (rc) return rc;
     lbvh_out b;
