@@ -39,6 +39,11 @@
 #include <type_traits>
 #include <vector>
 
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#include "detail/vrh_pixel.h"      // depth_transform, for user kernels into targets with a depth buffer
+#endif
+
 namespace visionaray
 {
 
@@ -543,26 +548,47 @@ private:
 };
 
 //-------------------------------------------------------------------------------------------------
-// hip_buffer_rt<CF, DF>: gpu_buffer_rt replacement.  Colour is RGBA32F; the render target also
-// keeps the closest-hit prim_id / t and the AO occlusion mask (the integer outputs used for parity).
+// hip_buffer_rt<CF, DF>: gpu_buffer_rt replacement.  The render target also keeps the closest-hit
+// prim_id / t and the AO occlusion mask (the integer outputs used for parity).
+// <PF_RGBA32F, PF_UNSPECIFIED> is the plain target (vrh_rt_alloc).  Every other pair -- PF_RGBA8, PF_RGB8,
+// PF_RGB32F or PF_RGBA32F colour with no, a PF_DEPTH32F or a PF_DEPTH24_STENCIL8 depth buffer -- is a formatted
+// target (vrh.h vrh_rt_alloc_formatted): frames render into its RGBA32F staging colour (ref().color, download())
+// and a resolve pass after every frame converts them into ref().formatted_color / ref().depth
+// (download_formatted()), as the reference's pixel_access::store / blend write a cpu_buffer_rt<CF, DF>.
 //
+
+namespace hip_detail
+{
+// vrh_color_format / vrh_depth_format of the reference's pixel_format values (pixel_format.h:15-60); -1: not taken
+constexpr int color_format_of(int pf) { return pf == 12 ? int(VRH_CF_RGBA32F) : pf == 11 ? int(VRH_CF_RGB32F) : pf == 4 ? int(VRH_CF_RGBA8) : pf == 3 ? int(VRH_CF_RGB8) : -1; }
+constexpr int depth_format_of(int pf) { return pf == 0 ? int(VRH_DF_NONE) : pf == 36 ? int(VRH_DF_DEPTH32F) : pf == 37 ? int(VRH_DF_DEPTH24_STENCIL8) : -1; }
+}
 
 template <auto ColorFormat, auto DepthFormat>
 class hip_buffer_rt
 {
-    // the formats of the measured configurations; other formats are a
-    // compile error rather than a silent RGBA32F target (values as in pixel_format.h:15-60)
-    static_assert(int(ColorFormat) == 12, "hip_buffer_rt: colour format PF_RGBA32F");
-    static_assert(int(DepthFormat) == 0, "hip_buffer_rt: depth format PF_UNSPECIFIED (no depth buffer)");
+    // other formats are a compile error rather than a silent RGBA32F target
+    static_assert(hip_detail::color_format_of(int(ColorFormat)) >= 0,
+                  "hip_buffer_rt: the colour format is one of PF_RGBA32F, PF_RGB32F, PF_RGBA8, PF_RGB8");
+    static_assert(hip_detail::depth_format_of(int(DepthFormat)) >= 0,
+                  "hip_buffer_rt: the depth format is one of PF_UNSPECIFIED (no depth buffer), PF_DEPTH32F, PF_DEPTH24_STENCIL8");
 
 public:
+    static constexpr uint32_t color_format = uint32_t(hip_detail::color_format_of(int(ColorFormat)));
+    static constexpr uint32_t depth_format = uint32_t(hip_detail::depth_format_of(int(DepthFormat)));
+    static constexpr bool formatted = color_format != VRH_CF_RGBA32F || depth_format != VRH_DF_NONE;
+    // bytes of one pixel of the formatted colour buffer (RGB32F: 16, the reference's vector<3, float>)
+    static constexpr size_t color_bytes = color_format == VRH_CF_RGBA8 ? 4 : color_format == VRH_CF_RGB8 ? 3 : 16;
+
     struct ref_type          // render_target_ref analogue: raw device pointers + size
     {
-        float* color;        // RGBA32F
+        float* color;        // RGBA32F: the frame as the kernels write it (a formatted target's staging colour)
         uint32_t* prim_id;
         float* t;
         uint8_t* occ;
         size_t width, height;
+        void* formatted_color;   // the buffer in ColorFormat (= color for the plain target)
+        void* depth;             // the buffer in DepthFormat, null for PF_UNSPECIFIED
     };
 
     explicit hip_buffer_rt(std::shared_ptr<hip_context> ctx = hip_context::default_context())
@@ -573,7 +599,13 @@ public:
     void resize(size_t w, size_t h)
     {
         vrh_rt* r = nullptr;
-        hip_detail::check(vrh_rt_alloc(ctx_->get(), uint32_t(w), uint32_t(h), VRH_RT_ALL, &r), "vrh_rt_alloc");
+        if constexpr (formatted)
+        {
+            const vrh_rt_format fmt{ color_format, depth_format };
+            hip_detail::check(vrh_rt_alloc_formatted(ctx_->get(), uint32_t(w), uint32_t(h), VRH_RT_ALL, &fmt, &r), "vrh_rt_alloc_formatted");
+        }
+        else
+            hip_detail::check(vrh_rt_alloc(ctx_->get(), uint32_t(w), uint32_t(h), VRH_RT_ALL, &r), "vrh_rt_alloc");
         rt_.reset(r, [](vrh_rt* p) { vrh_rt_free(p); });
         width_ = w;
         height_ = h;
@@ -594,6 +626,13 @@ public:
         hip_detail::check(vrh_rt_clear(ctx_->get(), rt_.get(), f), "vrh_rt_clear");
     }
 
+    // clear_depth_buffer (detail/simple_buffer_rt.inl:68-80)
+    void clear_depth_buffer(float depth = 1.0f)
+    {
+        static_assert(depth_format != VRH_DF_NONE, "hip_buffer_rt::clear_depth_buffer: the target has no depth buffer");
+        hip_detail::check(vrh_rt_clear_depth(ctx_->get(), rt_.get(), depth), "vrh_rt_clear_depth");
+    }
+
     void begin_frame() {}
     // end_frame() synchronises, so hip_sched::frame blocks like tiled_sched::frame -- unless the
     // context issues frames asynchronously (hip_context::set_async_frames): then it returns at once,
@@ -611,6 +650,7 @@ public:
         r.color = static_cast<float*>(c);
         r.width = width_;
         r.height = height_;
+        hip_detail::check(vrh_rt_get_formatted(rt_.get(), &r.formatted_color, &r.depth, nullptr), "vrh_rt_get_formatted");
         return r;
     }
 
@@ -618,6 +658,14 @@ public:
     void download(float* rgba, uint32_t* prim_id = nullptr, float* t = nullptr, uint8_t* occ = nullptr)
     {
         hip_detail::check(vrh_rt_download(ctx_->get(), rt_.get(), rgba, prim_id, t, occ), "vrh_rt_download");
+        ctx_->check_user_walks();
+    }
+
+    // the formatted buffers: width * height pixels of color_bytes, and 4-byte depth words (either may be null)
+    void download_formatted(void* color, void* depth = nullptr)
+    {
+        static_assert(formatted, "hip_buffer_rt::download_formatted: <PF_RGBA32F, PF_UNSPECIFIED> is the plain target (download)");
+        hip_detail::check(vrh_rt_download_formatted(ctx_->get(), rt_.get(), color, depth), "vrh_rt_download_formatted");
         ctx_->check_user_walks();
     }
 
@@ -1109,6 +1157,43 @@ hip_builtin_kernel make_hip_multi_hit_kernel(NormalBinding const& binding, BVH c
 // hip_sched<R>: cuda_sched<R> replacement (persistent-thread HIP kernels, tile work stealing)
 //
 
+namespace hip_detail
+{
+template <typename RT, typename = void> struct is_formatted_rt : std::false_type {};
+template <typename RT> struct is_formatted_rt<RT, typename std::enable_if<RT::formatted>::type> : std::true_type {};
+
+// sched_params with the jittered sampler in place of their own: everything else -- camera or matrices, target,
+// scissor box, intersector -- is SP's
+template <typename SP>
+struct as_jittered : SP
+{
+    using pixel_sampler_type = pixel_sampler::jittered_type;
+    explicit as_jittered(SP const& sp) : SP(sp) {}
+};
+
+// A user kernel whose result carries the depth the reference's sample_pixel_impl gives it before it stores into a
+// target with a depth buffer (sched_common.h:425): depth = hit ? depth_transform(isect_pos, view, proj) : 1.
+// Device code: defined where hipcc compiles the header (with hip_kernels.h, which user kernels need anyway).
+template <typename K> struct with_depth;
+#if defined(__HIPCC__)
+template <typename K>
+struct with_depth
+{
+    K kernel;
+    float view[16], proj[16];     // column-major
+
+    template <typename... A>
+    __device__ auto operator()(A&&... a) -> decltype(kernel(std::forward<A>(a)...))
+    {
+        auto result = kernel(std::forward<A>(a)...);
+        const float pos[3] = { result.isect_pos.x, result.isect_pos.y, result.isect_pos.z };
+        result.depth = result.hit ? vrh::dev::depth_transform(pos, view, proj) : 1.0f;
+        return result;
+    }
+};
+#endif
+}
+
 template <typename R>
 class hip_sched
 {
@@ -1198,7 +1283,7 @@ public:
                           "make_hip_pathtracing_kernel) through the C ABI; a user kernel "
                           "(a callable) is device code: include visionaray_hip/hip_kernels.h and compile with hipcc");
             if (shard) throw std::runtime_error("hip_sched::frame: user kernels render the whole image");
-            hip_detail::user_kernels<K>::frame(*ctx_, kernel, sparams, frame_num);
+            frame_user(kernel, sparams, frame_num);
             return;
         }
         else
@@ -1206,6 +1291,67 @@ public:
     }
 
 private:
+    // A user kernel's frame.  Into a formatted target the launch (hip_kernels.h) writes the staging buffers and the
+    // resolve pass the runtime runs after a built-in frame follows it here, on the context's stream, over the launch's
+    // scissor box and with the launch's sampler:
+    //   uniform, jittered   the frame is stored;
+    //   jittered_blend      the launch runs with the jittered sampler -- the same ray, the sample stored in the
+    //                       staging buffers -- and the resolve blends it with 1 / frame_num, 1 - 1 / frame_num onto
+    //                       the formatted buffers, whose quantised contents accumulate as in the reference;
+    //   ssaa                refused, as for the built-in kernels.
+    // A target with a depth format takes camera matrices, as in the reference (sched_common.h:399-439): the kernel is
+    // wrapped so that its result carries depth = hit ? depth_transform(isect_pos, view, proj) : 1, the launch stores
+    // that in the staging t buffer, and the resolve converts or blends it (vrh_resolve_desc::matrix_cam 0).
+    template <typename K, typename SP>
+    void frame_user(K const& kernel, SP& sparams, unsigned frame_num)
+    {
+        using RT = typename std::decay<decltype(sparams.rt)>::type;
+        if constexpr (!hip_detail::is_formatted_rt<RT>::value)
+            hip_detail::user_kernels<K>::frame(*ctx_, kernel, sparams, frame_num);
+        else
+        {
+            using PS = hip_detail::sampler_desc<typename hip_detail::sampler_of<SP>::type>;
+            if (PS::kind == VRH_SAMPLER_SSAA)
+                throw std::runtime_error("hip_sched::frame: the ssaa sampler does not render into a formatted render target");
+            vrh_resolve_desc d{};
+            d.s = 1.0f;
+            vrh_camera c{};
+            hip_detail::set_scissor(sparams, c);
+            std::memcpy(d.scissor, c.scissor, sizeof(d.scissor));
+            if constexpr (PS::kind == VRH_SAMPLER_JITTERED_BLEND)
+            {
+                hip_detail::as_jittered<SP> jittered(sparams);
+                launch_user(kernel, jittered, frame_num);
+                d.blend = 1u;
+                d.s = 1.0f / float(frame_num);
+                d.d = 1.0f - d.s;
+            }
+            else
+                launch_user(kernel, sparams, frame_num);
+            hip_detail::check(vrh_rt_resolve(ctx_->get(), sparams.rt.handle(), &d), "vrh_rt_resolve");
+            sparams.rt.end_frame();
+        }
+    }
+
+    template <typename K, typename SP>
+    void launch_user(K const& kernel, SP& sparams, unsigned frame_num)
+    {
+        using RT = typename std::decay<decltype(sparams.rt)>::type;
+        if constexpr (RT::depth_format == VRH_DF_NONE)
+            hip_detail::user_kernels<K>::frame(*ctx_, kernel, sparams, frame_num);
+        else if constexpr (!hip_detail::has_camera_matrices<SP>::value)
+            throw std::runtime_error("hip_sched::frame: a render target with a depth format is rendered through camera matrices "
+                                     "(make_sched_params(sampler, view_matrix, proj_matrix, rt))");
+        else
+        {
+            using D = hip_detail::with_depth<K>;
+            D wrapped{ kernel, {}, {} };
+            std::memcpy(wrapped.view, sparams.view_matrix.data(), sizeof(wrapped.view));
+            std::memcpy(wrapped.proj, sparams.proj_matrix.data(), sizeof(wrapped.proj));
+            hip_detail::user_kernels<D>::frame(*ctx_, wrapped, sparams, frame_num);
+        }
+    }
+
     // the volume kernels (vrh_render_volume, vrh_render_multi_volume): the uniform sampler and a pinhole camera, whole
     // image or scissor box
     template <typename VK, typename SP>
@@ -1305,6 +1451,9 @@ public:
             static_assert(hip_detail::user_kernels<K>::available,
                           "hip_sched::frames: a user kernel (a callable) is device code: include "
                           "visionaray_hip/hip_kernels.h and compile with hipcc");
+            // (several frames in one target: refused for a formatted target, as vrh_render_batch refuses them)
+            if (hip_detail::is_formatted_rt<RT>::value)
+                throw std::runtime_error("hip_sched::frames: a formatted render target takes one frame per call, not a batch");
             hip_detail::user_kernels<K>::frames(*ctx_, kernel, cams, rt, frame_num);
         }
         else

@@ -30,7 +30,11 @@
 namespace visionaray
 {
 
-enum pixel_format { PF_UNSPECIFIED = 0, PF_RGBA32F = 12 };   // the reference's values (pixel_format.h:15-60)
+// the reference's values (pixel_format.h:15-60): the formats hip_buffer_rt<CF, DF> takes
+enum pixel_format
+{
+    PF_UNSPECIFIED = 0, PF_RGB8 = 3, PF_RGBA8 = 4, PF_RGB32F = 11, PF_RGBA32F = 12, PF_DEPTH32F = 36, PF_DEPTH24_STENCIL8 = 37
+};
 
 //-------------------------------------------------------------------------------------------------
 // vector<N, T> (math/vector.h): vec2 / vec3 / vec4 with the reference's member names.  vec3 is

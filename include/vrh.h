@@ -791,6 +791,69 @@ VRH_API int vrh_rt_download(vrh_ctx* ctx, vrh_rt* rt, void* color, uint32_t* pri
 VRH_API int vrh_rt_upload(vrh_ctx* ctx, vrh_rt* rt, const void* color, const uint32_t* prim_id, const float* t,
                           const uint8_t* occ);
 
+/* ---- formatted render targets -------------------------------------------------------------------
+ * Render targets in the reference's other pixel formats (pixel_format.h; cpu_buffer_rt<CF, DF>,
+ * gpu_buffer_rt<CF, DF>): RGBA8, RGB8, RGB32F or RGBA32F colour with no, a DEPTH32F or a DEPTH24_STENCIL8
+ * depth buffer.  A formatted target owns RGBA32F staging colour, prim_id and t buffers (allocated whatever
+ * `flags` say), into which every frame renders exactly as into a plain target (vrh_rt_download,
+ * vrh_rt_upload and vrh_rt_get_buffers address them), and the formatted buffers, into which a resolve pass on
+ * the frame's stream, right after the frame's kernel, stores or blends the frame as the reference's
+ * pixel_access::store / blend do (visionaray_hip/detail/vrh_pixel.h has the conversions):
+ *   RGBA8   4 bytes r g b a, uint8(double(clamp(c, 0, 1)) * 255.0), truncated
+ *   RGB8    3 bytes r g b, no padding; rgb * a first
+ *   RGB32F  16 bytes: rgb * a, and a fourth word that is written as 0 (unspecified in the reference)
+ *   RGBA32F 16 bytes, the frame's colour
+ *   DEPTH32F / DEPTH24_STENCIL8  4 bytes: (z + 1) / 2 of the hit point under proj * view, 1.0 for a miss;
+ *           uint32(depth * 16777215.0f) << 8 for the latter (the conversion saturates; NaN gives 0)
+ * With a formatted target:
+ *   vrh_render, vrh_render_volume, vrh_render_multi_volume   render, then store (colour formats only)
+ *   vrh_render_sampled   uniform and jittered store; jittered_blend renders the frame's sample into the staging
+ *                        buffers and blends it onto the formatted ones with 1 / frame_num, 1 - 1 / frame_num
+ *                        (the quantised buffer is what accumulates, as in the reference); ssaa: VRH_ERR_UNSUPPORTED
+ *   vrh_render_view      the same, and the only entry point that takes a target with a depth format (the
+ *                        reference computes a depth on the matrix path only); any other: VRH_ERR_UNSUPPORTED
+ *   vrh_render_batch with more than one frame, shards, render groups (vrh_render_sharded, vrh_unshard):
+ *                        VRH_ERR_UNSUPPORTED, before anything is launched, the target untouched
+ *   vrh_rt_clear         clears the staging colour and stores the converted colour into the formatted buffer
+ *                        (clear_color_buffer, detail/simple_buffer_rt.inl:54-66)
+ *   vrh_last_frame_stats kernel_ms covers the frame's kernel and its resolve pass */
+enum vrh_color_format { VRH_CF_RGBA32F = 0, VRH_CF_RGB32F = 1, VRH_CF_RGBA8 = 2, VRH_CF_RGB8 = 3 };
+enum vrh_depth_format { VRH_DF_NONE = 0, VRH_DF_DEPTH32F = 1, VRH_DF_DEPTH24_STENCIL8 = 2 };
+typedef struct { uint32_t color_format, depth_format; } vrh_rt_format;
+VRH_API int vrh_rt_alloc_formatted(vrh_ctx* ctx, uint32_t w, uint32_t h, uint32_t flags, const vrh_rt_format* format,
+                                   vrh_rt** out);
+/* the formatted buffers (device pointers; depth NULL without a depth format) and the format; a plain target
+ * reports its colour buffer as VRH_CF_RGBA32F / VRH_DF_NONE.  Any out pointer may be NULL */
+VRH_API int vrh_rt_get_formatted(const vrh_rt* rt, void** color, void** depth, vrh_rt_format* format);
+/* copies of the formatted buffers (either may be NULL): width * height elements; synchronous */
+VRH_API int vrh_rt_download_formatted(vrh_ctx* ctx, vrh_rt* rt, void* color, void* depth);
+VRH_API int vrh_rt_upload_formatted(vrh_ctx* ctx, vrh_rt* rt, const void* color, const void* depth);
+/* clear_depth_buffer (detail/simple_buffer_rt.inl:68-80): every pixel's depth = the converted value */
+VRH_API int vrh_rt_clear_depth(vrh_ctx* ctx, vrh_rt* rt, float depth);
+/* The resolve pass the runtime runs after a frame, for launches of one's own (the user kernels of
+ * visionaray_hip/hip_kernels.h) and tests: staging buffers -> formatted buffers over the scissor box, every
+ * other pixel untouched.  The depth of a target with a depth format is that of the matrix camera's ray of the
+ * pixel -- view, proj, jitter, frame_num, px_off as the frame had them (matrix_cam 1) -- at the
+ * staging t, 1.0 where the staging prim_id is 0xFFFFFFFF.  With matrix_cam 0 the staging t buffer holds the
+ * depth itself (what a user kernel's launch stores there: result.depth) and is stored or blended as it is;
+ * prim_id is then not read.  Asynchronous, ordered like a frame on the context's stream. */
+typedef struct {
+    uint32_t blend;             /* 0 store, 1 blend: dst = src * s + dst * d, then stored               */
+    float    s, d;
+    uint32_t scissor[4];        /* x0, y0, x1, y1 (exclusive edges); all zero: whole image              */
+    uint32_t matrix_cam;        /* 1: view / proj are set; 0 with a depth format: staging t is the depth */
+    float    view[16], proj[16];/* column-major, as vrh_view_camera                                     */
+    uint32_t jitter, frame_num; /* jitter 1: the jittered samplers' ray of frame frame_num              */
+    float    px_off[2];         /* jitter 0: the sub-pixel offset added to (x, y)                       */
+} vrh_resolve_desc;
+VRH_API int vrh_rt_resolve(vrh_ctx* ctx, vrh_rt* rt, const vrh_resolve_desc* desc);
+/* the host build of the same text (no device needed): color width * height RGBA32F, prim_id and t
+ * width * height entries (needed with a depth format only), color_out / depth_out the formatted arrays, read
+ * (blend) and written over the scissor box */
+VRH_API int vrh_rt_resolve_host(const vrh_rt_format* format, uint32_t w, uint32_t h, const float* color,
+                                const uint32_t* prim_id, const float* t, const vrh_resolve_desc* desc,
+                                void* color_out, void* depth_out);
+
 /* multi-GPU: number of bands shard g of N owns, and the root-side un-interleave of N gathered
  * packed shards into a full target.  Shard g's array starts at base + g * shard_stride_bytes
  * (0 = dense [N][rows][W], rows = VRH_BAND_ROWS * vrh_shard_bands(H, 0, N)) and holds rows x W

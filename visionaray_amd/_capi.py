@@ -94,6 +94,20 @@ class vrh_view_camera(C.Structure):
                 ("scissor", C.c_uint32 * 4)]
 
 
+VRH_CF_RGBA32F, VRH_CF_RGB32F, VRH_CF_RGBA8, VRH_CF_RGB8 = 0, 1, 2, 3
+VRH_DF_NONE, VRH_DF_DEPTH32F, VRH_DF_DEPTH24_STENCIL8 = 0, 1, 2
+
+
+class vrh_rt_format(C.Structure):
+    _fields_ = [("color_format", C.c_uint32), ("depth_format", C.c_uint32)]
+
+
+class vrh_resolve_desc(C.Structure):
+    _fields_ = [("blend", C.c_uint32), ("s", C.c_float), ("d", C.c_float), ("scissor", C.c_uint32 * 4),
+                ("matrix_cam", C.c_uint32), ("view", C.c_float * 16), ("proj", C.c_float * 16),
+                ("jitter", C.c_uint32), ("frame_num", C.c_uint32), ("px_off", C.c_float * 2)]
+
+
 class vrh_shard(C.Structure):
     _fields_ = [("index", C.c_uint32), ("count", C.c_uint32), ("packed", C.c_uint32), ("reserved", C.c_uint32)]
 
@@ -272,6 +286,14 @@ SIGNATURES = {
     "vrh_get_accum_stats": (C.c_int, [_vp, C.POINTER(vrh_accum_stats)]),
     "vrh_rt_download": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "vrh_rt_upload": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "vrh_rt_alloc_formatted": (C.c_int, [_vp, _u32, _u32, _u32, C.POINTER(vrh_rt_format), C.POINTER(_vp)]),
+    "vrh_rt_get_formatted": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(vrh_rt_format)]),
+    "vrh_rt_download_formatted": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "vrh_rt_upload_formatted": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "vrh_rt_clear_depth": (C.c_int, [_vp, _vp, C.c_float]),
+    "vrh_rt_resolve": (C.c_int, [_vp, _vp, C.POINTER(vrh_resolve_desc)]),
+    "vrh_rt_resolve_host": (C.c_int, [C.POINTER(vrh_rt_format), _u32, _u32, _vp, _vp, _vp, C.POINTER(vrh_resolve_desc),
+                                      _vp, _vp]),
     "vrh_shard_bands": (C.c_uint32, [_u32, _u32, _u32]),
     "vrh_unshard": (C.c_int, [_vp, _u32, _u32, _u32, _vp, _vp, _vp, C.c_uint64, C.POINTER(vrh_kernel_desc), _vp]),
     "vrh_build_bvh": (C.c_int, [_vp, _u32, _u32, _vp, C.POINTER(_u32), _vp, C.POINTER(_u32)]),

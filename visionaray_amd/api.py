@@ -359,23 +359,54 @@ class hip_index_bvh:
             pass
 
 
+class color_format:
+    """vrh_color_format: the reference's PF_RGBA32F, PF_RGB32F, PF_RGBA8, PF_RGB8."""
+    rgba32f, rgb32f, rgba8, rgb8 = capi.VRH_CF_RGBA32F, capi.VRH_CF_RGB32F, capi.VRH_CF_RGBA8, capi.VRH_CF_RGB8
+
+
+class depth_format:
+    """vrh_depth_format: PF_UNSPECIFIED, PF_DEPTH32F, PF_DEPTH24_STENCIL8."""
+    none, depth32f, depth24_stencil8 = capi.VRH_DF_NONE, capi.VRH_DF_DEPTH32F, capi.VRH_DF_DEPTH24_STENCIL8
+
+
+def _formatted_arrays(cf, df, n):
+    """Host arrays of n pixels in a colour / depth format: (n, 4) u8, (n, 3) u8 or (n, 4) f32 (RGB32F: 16-byte
+    elements whose fourth word is padding), and n f32 / u32 depth words or None."""
+    color = np.zeros((n, 4 if cf == capi.VRH_CF_RGBA8 else 3), np.uint8) if cf in (capi.VRH_CF_RGBA8, capi.VRH_CF_RGB8) \
+        else np.zeros((n, 4), np.float32)
+    depth = None if df == capi.VRH_DF_NONE else np.zeros(n, np.float32 if df == capi.VRH_DF_DEPTH32F else np.uint32)
+    return color, depth
+
+
 class hip_buffer_rt:
-    """gpu_buffer_rt<PF_RGBA32F, PF_UNSPECIFIED> plus the integer side buffers used for parity.
+    """gpu_buffer_rt<CF, DF> plus the integer side buffers used for parity.  The default, RGBA32F colour and no
+    depth, is the plain target; any other color_format / depth_format (color_format.*, depth_format.*) makes a
+    formatted target (vrh_rt_alloc_formatted): frames render into its RGBA32F staging buffers (download(),
+    upload()) and are resolved into the formatted buffers (download_formatted()).  formatted=True asks for a
+    formatted target of the default pair too (an RGBA32F copy of the staging colour).
 
     wrap=(color_ptr, prim_id_ptr, t_ptr, occ_ptr) borrows caller device memory (e.g. torch tensors).
     """
 
-    def __init__(self, ctx, width, height, flags=capi.VRH_RT_ALL, wrap=None):
+    def __init__(self, ctx, width, height, flags=capi.VRH_RT_ALL, wrap=None, color_format=capi.VRH_CF_RGBA32F,
+                 depth_format=capi.VRH_DF_NONE, formatted=None):
         self.ctx = ctx
         self.handle = None
         self.flags = flags
         self._wrap = wrap
+        self.color_format, self.depth_format = int(color_format), int(depth_format)
+        self.formatted = bool(formatted) or (self.color_format, self.depth_format) != (capi.VRH_CF_RGBA32F, capi.VRH_DF_NONE)
+        if self.formatted and wrap is not None:
+            raise ValueError("hip_buffer_rt: a formatted render target owns its buffers (no wrap)")
         self.resize(width, height)
 
     def resize(self, width, height):
         self.close()
         h = C.c_void_p()
-        if self._wrap is None:
+        if self.formatted:
+            fmt = capi.vrh_rt_format(self.color_format, self.depth_format)
+            capi.check("vrh_rt_alloc_formatted", self.ctx.handle, width, height, self.flags, C.byref(fmt), C.byref(h))
+        elif self._wrap is None:
             capi.check("vrh_rt_alloc", self.ctx.handle, width, height, self.flags, C.byref(h))
         else:
             c, p, t, o = (C.c_void_p(x) if x else None for x in self._wrap)
@@ -391,6 +422,27 @@ class hip_buffer_rt:
 
     def clear_color_buffer(self, color=(0.0, 0.0, 0.0, 0.0)):
         capi.check("vrh_rt_clear", self.ctx.handle, self.handle, (C.c_float * 4)(*color))
+
+    def clear_depth_buffer(self, depth=1.0):
+        capi.check("vrh_rt_clear_depth", self.ctx.handle, self.handle, float(depth))
+
+    def download_formatted(self):
+        """The formatted buffers: {"color": (n, 4) u8 | (n, 3) u8 | (n, 4) f32, "depth": n f32 | u32 (if any)}."""
+        color, depth = _formatted_arrays(self.color_format, self.depth_format, self.w * self.h)
+        capi.check("vrh_rt_download_formatted", self.ctx.handle, self.handle, _p(color), _p(depth))
+        return {"color": color} if depth is None else {"color": color, "depth": depth}
+
+    def upload_formatted(self, color=None, depth=None):
+        ref = _formatted_arrays(self.color_format, self.depth_format, self.w * self.h)
+        arrs = [None if a is None else np.ascontiguousarray(a) for a in (color, depth)]
+        for a, r in zip(arrs, ref):
+            if a is not None and (r is None or a.nbytes != r.nbytes):
+                raise ValueError("upload_formatted: array size does not match the render target")
+        capi.check("vrh_rt_upload_formatted", self.ctx.handle, self.handle, *[_p(a) for a in arrs])
+
+    def resolve(self, desc):
+        """vrh_rt_resolve: the resolve pass a frame runs, for launches of one's own (a resolve_desc)."""
+        capi.check("vrh_rt_resolve", self.ctx.handle, self.handle, C.byref(desc))
 
     def begin_frame(self):
         pass
@@ -1272,6 +1324,44 @@ def render_view(ctx, bvh, rt, view_cam, kernel, sampler=pixel_sampler.uniform_ty
     ps = capi.vrh_pixel_sampler(sampler.kind, sampler.count)
     capi.check("vrh_render_view", ctx.handle, bvh.handle, rt.handle, C.byref(view_cam), C.byref(kernel.desc),
                C.byref(ps), frame_num)
+
+
+def resolve_desc(blend=False, s=1.0, d=0.0, scissor=(0, 0, 0, 0), view=None, proj=None, jitter=False, frame_num=0,
+                 px_off=(0.0, 0.0)):
+    """vrh_resolve_desc; view / proj (both or neither) as view_camera takes them."""
+    rd = capi.vrh_resolve_desc()
+    rd.blend, rd.s, rd.d = int(bool(blend)), float(s), float(d)
+    rd.scissor[:] = [int(x) for x in scissor]
+    if view is not None:
+        rd.matrix_cam = 1
+        rd.view[:] = [float(x) for x in _matrix4(view)]
+        rd.proj[:] = [float(x) for x in _matrix4(proj)]
+    rd.jitter, rd.frame_num = int(bool(jitter)), int(frame_num)
+    rd.px_off[:] = [float(x) for x in px_off]
+    return rd
+
+
+def rt_resolve_host(color_fmt, depth_fmt, width, height, color, desc, prim_id=None, t=None, color_out=None, depth_out=None):
+    """vrh_rt_resolve_host: the host build of the resolve pass.  color (n, 4) f32 staging colour, prim_id / t the
+    staging side buffers (needed with a depth format); color_out / depth_out: the formatted arrays before the pass
+    (zeros if None; not modified).  Returns {"color": ..., "depth": ...} as download_formatted does."""
+    n = width * height
+    co, do = _formatted_arrays(color_fmt, depth_fmt, n)
+    if color_out is not None:
+        co[...] = np.asarray(color_out).reshape(co.shape)
+    if do is not None and depth_out is not None:
+        do[...] = np.asarray(depth_out).reshape(do.shape)
+    color = np.ascontiguousarray(color, np.float32)
+    if color.size != n * 4:
+        raise ValueError("rt_resolve_host: colour must hold width * height RGBA32F pixels")
+    pid = None if prim_id is None else np.ascontiguousarray(prim_id, np.uint32)
+    tt = None if t is None else np.ascontiguousarray(t, np.float32)
+    for a in (pid, tt):
+        if a is not None and a.size != n:
+            raise ValueError("rt_resolve_host: prim_id / t must hold width * height entries")
+    fmt = capi.vrh_rt_format(int(color_fmt), int(depth_fmt))
+    capi.check("vrh_rt_resolve_host", C.byref(fmt), width, height, _p(color), _p(pid), _p(tt), C.byref(desc), _p(co), _p(do))
+    return {"color": co} if do is None else {"color": co, "depth": do}
 
 
 def matrix_inverse(m):

@@ -386,6 +386,7 @@ VRH_API int vrh_render_sharded(uint32_t n, vrh_group* const* groups, const vrh_s
     {
         VRH_CHECK(dst && dst->ctx == groups[root]->ctx, "vrh_render_sharded: the root needs a target on its context");
         VRH_CHECK(dst->width == W && dst->height == H * num_frames, "vrh_render_sharded: target must be W x (H * frames)");
+        if (dst->formatted) { set_error("vrh_render_sharded: a formatted render target is no render group destination"); return VRH_ERR_UNSUPPORTED; }
         VRH_CHECK((!(fields & VRH_RT_COLOR) || dst->color) && (!(fields & VRH_RT_PRIM_ID) || dst->prim_id) &&
                   (!(fields & VRH_RT_T) || dst->t) && (!(fields & VRH_RT_OCC) || dst->occ),
                   "vrh_render_sharded: the target lacks a buffer named in fields");

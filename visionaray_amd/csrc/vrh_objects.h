@@ -156,6 +156,12 @@ struct vrh_rt
     hipEvent_t lane_written = nullptr;
     int lane = -1;
     uint64_t lane_epoch = 0;
+    // a formatted target (vrh_rt_alloc_formatted): colour / prim_id / t above are its staging buffers, and a
+    // resolve pass after every frame converts them into these (vrh_resolve.hip); always owned
+    bool formatted = false;
+    uint32_t color_format = 0, depth_format = 0;    // vrh_color_format, vrh_depth_format
+    void* fcolor = nullptr;
+    void* fdepth = nullptr;
 };
 
 // a render group's root wrote `rt` on `stream`: record it so the target's own context orders after

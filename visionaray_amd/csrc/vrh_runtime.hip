@@ -10,6 +10,7 @@
 #include "vrh_plan.h"
 #include "vrh_lbvh.h"
 #include "vrh_texhost.h"
+#include "vrh_resolve.h"
 
 #include <hip/hip_runtime.h>
 
@@ -879,6 +880,12 @@ VRH_API int vrh_rt_free(vrh_rt* rt)
         if (rt->t) (void)hipFree(rt->t);
         if (rt->occ) (void)hipFree(rt->occ);
     }
+    if (rt->fcolor || rt->fdepth)
+    {
+        if (rt->ctx) (void)hipSetDevice(rt->ctx->device);
+        if (rt->fcolor) (void)hipFree(rt->fcolor);
+        if (rt->fdepth) (void)hipFree(rt->fdepth);
+    }
     if (rt->mh_prim_id || rt->mh_t)
     {
         if (rt->ctx) (void)hipSetDevice(rt->ctx->device);
@@ -989,6 +996,8 @@ VRH_API int vrh_rt_clear(vrh_ctx* ctx, vrh_rt* rt, const float color[4])
     hipLaunchKernelGGL(fill_rt_kernel, dim3(unsigned((n + 255) / 256)), dim3(256), 0, ctx->stream,
                        rt->color, rt->prim_id, rt->t, rt->occ, n, c);
     VRH_HIP(hipGetLastError());
+    // a formatted target: clear_color_buffer stores the converted colour (simple_buffer_rt.inl:54-66)
+    if (rt->formatted) return resolve_clear_color(rt, color, ctx->stream);
     return VRH_OK;
 }
 
@@ -1013,6 +1022,7 @@ struct sampler_pass
     uint32_t jitter, blend;
     float s, d;
     const float* inv_mats;    // vrh_render_view: inverse view, inverse projection (32 floats), else null
+    const float* mats;        // vrh_render_view: view, projection (a formatted target's depth), else null
 };
 int render_batch_impl(vrh_ctx* ctx, const vrh_scene* sc, vrh_rt* rt, const vrh_camera* cams, uint32_t num_frames,
                       const vrh_kernel_desc* k, const vrh_shard* shard, uint32_t frame_num, const sampler_pass* sp);
@@ -1028,10 +1038,17 @@ VRH_API int vrh_render_batch(vrh_ctx* ctx, const vrh_scene* sc, vrh_rt* rt, cons
 namespace {
 // the passes of a pixel sampler (vrh_render_sampled / vrh_render_view); inv_mats: camera matrices
 int render_sampled_impl(vrh_ctx* ctx, const vrh_scene* sc, vrh_rt* rt, const vrh_camera* cam,
-                        const vrh_kernel_desc* k, const vrh_pixel_sampler* ps, uint32_t frame_num, const float* inv_mats)
+                        const vrh_kernel_desc* k, const vrh_pixel_sampler* ps, uint32_t frame_num, const float* inv_mats,
+                        const float* mats)
 {
     VRH_CHECK(ctx && sc && rt && cam && k && ps, "vrh_render_sampled: null argument");
     VRH_CHECK(ps->kind <= VRH_SAMPLER_SSAA, "vrh_render_sampled: unknown pixel sampler");
+    if (rt->formatted && ps->kind == VRH_SAMPLER_SSAA)
+    {
+        // the reference begins ssaa by storing a default-constructed result_record, whose depth it never defines
+        set_error(std::string(inv_mats ? "vrh_render_view" : "vrh_render_sampled") + ": the ssaa sampler does not render into a formatted render target");
+        return VRH_ERR_UNSUPPORTED;
+    }
     if (ps->kind == VRH_SAMPLER_UNIFORM && !inv_mats) return render_batch_impl(ctx, sc, rt, cam, 1, k, nullptr, frame_num, nullptr);
     if (k->kind == VRH_KERNEL_PATHTRACING && (inv_mats || ps->kind == VRH_SAMPLER_SSAA))
     {
@@ -1050,7 +1067,7 @@ int render_sampled_impl(vrh_ctx* ctx, const vrh_scene* sc, vrh_rt* rt, const vrh
     {
         // uniform (camera matrices): the pixel's ray, colour stored; jittered: the pixel's jittered
         // ray, colour stored; jittered_blend: blended with a = 1 / frame_num, 1 - a (sched_common.h:480-540)
-        sampler_pass p{ { 0.0f, 0.0f }, ps->kind == VRH_SAMPLER_UNIFORM ? 0u : 1u, 0u, 1.0f, 0.0f, inv_mats };
+        sampler_pass p{ { 0.0f, 0.0f }, ps->kind == VRH_SAMPLER_UNIFORM ? 0u : 1u, 0u, 1.0f, 0.0f, inv_mats, mats };
         if (ps->kind == VRH_SAMPLER_JITTERED_BLEND)
         {
             p.blend = 1u;
@@ -1069,7 +1086,7 @@ int render_sampled_impl(vrh_ctx* ctx, const vrh_scene* sc, vrh_rt* rt, const vrh
     const float (*tab)[2] = ps->count == 2 ? off2 : ps->count == 4 ? off4 : off8;
     for (uint32_t i = 0; i < ps->count; ++i)
     {
-        sampler_pass p{ { tab[i][0], tab[i][1] }, 0u, i == 0 ? 2u : 1u, 1.0f / float(ps->count), 1.0f, inv_mats };
+        sampler_pass p{ { tab[i][0], tab[i][1] }, 0u, i == 0 ? 2u : 1u, 1.0f / float(ps->count), 1.0f, inv_mats, mats };
         const int rc = render_batch_impl(ctx, sc, rt, cam, 1, k, nullptr, frame_num, &p);
         if (rc) return rc;
     }
@@ -1080,7 +1097,7 @@ int render_sampled_impl(vrh_ctx* ctx, const vrh_scene* sc, vrh_rt* rt, const vrh
 VRH_API int vrh_render_sampled(vrh_ctx* ctx, const vrh_scene* sc, vrh_rt* rt, const vrh_camera* cam,
                                const vrh_kernel_desc* k, const vrh_pixel_sampler* ps, uint32_t frame_num)
 {
-    return render_sampled_impl(ctx, sc, rt, cam, k, ps, frame_num, nullptr);
+    return render_sampled_impl(ctx, sc, rt, cam, k, ps, frame_num, nullptr, nullptr);
 }
 
 // matrix4.inl:209-244 inverse(): the 2x2 sub-determinants of rows 0-1 and 2-3
@@ -1118,7 +1135,10 @@ VRH_API int vrh_render_view(vrh_ctx* ctx, const vrh_scene* sc, vrh_rt* rt, const
     float inv[32];
     vrh_matrix_inverse(vc->view, inv);
     vrh_matrix_inverse(vc->proj, inv + 16);
-    return render_sampled_impl(ctx, sc, rt, &cam, k, ps, frame_num, inv);
+    float mats[32];
+    std::memcpy(mats, vc->view, sizeof(vc->view));
+    std::memcpy(mats + 16, vc->proj, sizeof(vc->proj));
+    return render_sampled_impl(ctx, sc, rt, &cam, k, ps, frame_num, inv, mats);
 }
 
 // ---- vrh_render: validate, plan (vrh_launch.h), fill render_params, choose where the launch runs,
@@ -1400,7 +1420,9 @@ int choose_site(vrh_ctx* ctx, vrh_rt* rt, const vrh_kernel_desc* k, uint32_t num
     // and it supersedes a pending scratch copy into this target of no larger box (that frame's pixels
     // would never be seen: they are dropped, not copied).  Any other pending copy into this target,
     // and one still in this lane's scratch target, is issued first.
-    const bool scratch_ok = num_frames == 1 && (k->kind == VRH_KERNEL_PRIMARY || k->kind == VRH_KERNEL_AO) && (!sp || sp->blend == 0);
+    // (a formatted target's resolve pass reads the frame where its kernel wrote it: never through the scratch target)
+    const bool scratch_ok = num_frames == 1 && (k->kind == VRH_KERNEL_PRIMARY || k->kind == VRH_KERNEL_AO) && (!sp || sp->blend == 0)
+                            && !rt->formatted;
     const uint32_t* cl = p.cam[0].clip;
     const bool* fields = site.fields;
     for (uint32_t l = 0; l < uint32_t(VRH_MAX_FRAME_LANES); ++l)
@@ -1471,7 +1493,10 @@ int launch_buffers(vrh_ctx* ctx, const launch_config& lc, uint32_t num_frames, i
     return VRH_OK;
 }
 
-int launch_and_record(vrh_ctx* ctx, vrh_rt* rt, const render_params& p, const launch_config& lc, int grid, const launch_site& site)
+// (rf: the resolve pass of a formatted target, on the launch's stream right after the frame's kernel, before the
+// target's lane_written event; null for a plain target)
+int launch_and_record(vrh_ctx* ctx, vrh_rt* rt, const render_params& p, const launch_config& lc, int grid, const launch_site& site,
+                      const resolve_frame* rf)
 {
     const hipStream_t S = site.stream;
     const uint32_t slot = ctx->frames % VRH_MAX_TIMED_FRAMES;
@@ -1486,6 +1511,9 @@ int launch_and_record(vrh_ctx* ctx, vrh_rt* rt, const render_params& p, const la
     VRH_HIP(hipMemsetAsync(site.counters, 0, COUNTERS_FRAME * sizeof(unsigned long long), S));
     VRH_HIP(hipEventRecord(ctx->ev_start[slot], S));
     if (p.num_tiles > 0) VRH_HIP(launch_render(p, lc, grid, S));
+    // (a resolve that could not be enqueued is reported after the frame's events and bookkeeping: the frame's
+    // kernel is in flight, and later frames must still be ordered after its writes)
+    const int resolve_rc = rf ? resolve_enqueue(rt, *rf, S) : VRH_OK;
     VRH_HIP(hipEventRecord(ctx->ev_stop[slot], S));
     if (vrh_ctx::lane_t* L = site.lane)
     {
@@ -1523,7 +1551,7 @@ int launch_and_record(vrh_ctx* ctx, vrh_rt* rt, const render_params& p, const la
     ctx->last.stack_depth = p.stack_total;
     ctx->last.frames = p.num_frames;
     ctx->have_frame = true;
-    return VRH_OK;
+    return resolve_rc;
 }
 
 int render_batch_impl(vrh_ctx* ctx, const vrh_scene* sc, vrh_rt* rt, const vrh_camera* cams, uint32_t num_frames,
@@ -1532,6 +1560,29 @@ int render_batch_impl(vrh_ctx* ctx, const vrh_scene* sc, vrh_rt* rt, const vrh_c
     frame_rows_t rows;
     int rc = validate_render(ctx, sc, rt, cams, num_frames, k, shard, rows);
     if (rc) return rc;
+    // a formatted target: whole single frames only, depth with the matrix camera only; the frame is rendered into
+    // the staging buffers with the sampler's blend forced to "store" (same jitter, offsets and frame number, so
+    // the same ray), and the resolve pass stores or blends it
+    sampler_pass staged;
+    resolve_frame rf{};
+    const bool formatted = rt->formatted;
+    if (formatted)
+    {
+        if (num_frames > 1) { set_error("vrh_render_batch: a formatted render target takes one frame per call, not a batch"); return VRH_ERR_UNSUPPORTED; }
+        if (shard) { set_error("vrh_render: a formatted render target takes whole frames, not shards"); return VRH_ERR_UNSUPPORTED; }
+        if ((rc = resolve_refuse(rt, sp && sp->inv_mats, "vrh_render"))) return rc;
+        rf.blend = sp ? sp->blend : 0u;
+        rf.s = sp ? sp->s : 1.0f; rf.d = sp ? sp->d : 0.0f;
+        rf.jitter = sp ? sp->jitter : 0u; rf.frame_num = frame_num;
+        if (sp)
+        {
+            rf.px_off[0] = sp->off[0]; rf.px_off[1] = sp->off[1];
+            rf.mats = sp->inv_mats ? sp->mats : nullptr; rf.inv_mats = sp->inv_mats;
+            staged = *sp;
+            staged.blend = 0u; staged.s = 1.0f; staged.d = 0.0f;
+            sp = &staged;
+        }
+    }
     rc = select_device(ctx);        // the plan's occupancy queries ask the context's device
     if (rc) return rc;
     launch_plan plan;
@@ -1559,7 +1610,8 @@ int render_batch_impl(vrh_ctx* ctx, const vrh_scene* sc, vrh_rt* rt, const vrh_c
     if (rc) return rc;
     rc = launch_buffers(ctx, plan.cfg, num_frames, grid, site, p);
     if (rc) return rc;
-    return launch_and_record(ctx, rt, p, plan.cfg, grid, site);
+    if (formatted) std::memcpy(rf.clip, p.cam[0].clip, sizeof(rf.clip));
+    return launch_and_record(ctx, rt, p, plan.cfg, grid, site, formatted ? &rf : nullptr);
 }
 } // namespace
 
@@ -1825,6 +1877,7 @@ VRH_API int vrh_unshard(vrh_ctx* ctx, uint32_t width, uint32_t height, uint32_t 
 {
     VRH_CHECK(ctx && dst && count >= 1, "vrh_unshard: bad argument");
     VRH_CHECK(dst->width == width && dst->height == height, "vrh_unshard: destination size mismatch");
+    if (dst->formatted) { set_error("vrh_unshard: a formatted render target is no unshard destination"); return VRH_ERR_UNSUPPORTED; }
     VRH_CHECK(gcolor || !dst->color || (gpid && k), "vrh_unshard: colour needs either gathered colour or prim ids + kernel");
     VRH_CHECK(gcolor || !dst->color || k->kind < VRH_KERNEL_SIMPLE,
               "vrh_unshard: shaded colour cannot be re-derived; gather the colour buffer");

@@ -100,6 +100,13 @@ inline std::string check_volume_kernel(const vrh_volume_kernel_desc& k, const vr
     return "";
 }
 
+// The entry points vrh_render_volume / vrh_render_multi_volume are compiled from vrh_volume.hip / vrh_multi_volume.hip
+// under the names vrh_render_volume_frame / vrh_render_multi_volume_frame (the Makefile passes -Dvrh_render_volume=...
+// to those two files, which also renames the declaration of vrh.h they see, and nothing else: no other identifier of
+// those names may be added to them).  vrh_resolve.hip defines the public entry points around them (a formatted
+// target's refusals, then the frame, then the resolve pass); csrc/vrh_exports.map keeps the inner names out of the
+// library's dynamic symbols.  Their own error texts keep the public names.
+
 // the scissor box of a camera clipped to the image: x0, y0, x1, y1
 inline void volume_clip(const vrh_camera& cam, uint32_t clip[4])
 {
