@@ -32,6 +32,7 @@
 
 #include "vrh_sampler.h"
 #include "vrh_fused_slab.h"
+#include "vrh_octant.h"
 
 // The AO kernel's 4-wide any-hit step (ray_step, QUAD_AO): its pushes go to the LDS part of the stack only (a ray
 // without LDS room restarts on the binary records), the other hit entries are pushed farthest first, and where
@@ -53,8 +54,12 @@ namespace dev {
 // section 4) and the AO step compares no link with QUAD_NONE; otherwise they repeat entry 0's box and the step compares.
 // KERNARG_STACK_CAP: the AO kernel's overflow-stack instances form the stack's LDS limit from the argument segment
 // before every step (vrh_kernels.hip kernarg_stack_cap) instead of holding it through the refill loop.
+// OCTANT_STEP: the AO step fetches each axis' near and far planes from the piece of the record that the sign of the
+// ray's inverse direction names, and forms tn / tf without sorting the plane distances (vrh_octant.h; every used
+// entry's box has lo <= hi, which build_quads checks, and a never-hit box has equal planes).
 constexpr bool NEVER_HIT_UNUSED = !VRH_FUSED_STEP;
 constexpr bool KERNARG_STACK_CAP = !VRH_FUSED_STEP;
+constexpr bool OCTANT_STEP = !VRH_FUSED_STEP;
 constexpr uint32_t LEAF_BIT = 0x80000000u;
 constexpr uint32_t END_BIT = 1u;
 constexpr int KIND_TRI = 0;
@@ -594,9 +599,36 @@ __device__ __forceinline__ int ray_step(const float4* __restrict__ pairs, const 
     {
         while (!(link & LEAF_BIT))
         {
-            const float4* p = quads + 8u * link;
-            const float4 xl = p[0], yl = p[1], zl = p[2], xh = p[3], yh = p[4], zh = p[5], lk = p[6];
-            if (COUNT) count_vmem(cnt, p, 7u, VMEM_QUAD);
+            // OCT (octant step): xl / yl / zl are the NEAR planes of the lane's ray and xh / yh / zh the FAR ones,
+            // each fetched from the piece the sign of r.inv names (vrh_octant.h) -- the record's base in a scalar
+            // register pair, the lane's byte offset in 32 bits (build_quads keeps a scene's records below 4 GiB)
+            constexpr bool OCT = QUAD_AO && OCTANT_STEP && !decltype(FZ)::value;
+            float4 xl, yl, zl, xh, yh, zh, lk;
+            if constexpr (OCT)
+            {
+                const char* qb = reinterpret_cast<const char*>(quads);
+                auto piece = [&](uint32_t off, uint32_t imm) { return *reinterpret_cast<const float4*>(qb + size_t(off) + imm); };
+                const uint32_t o = link * octant::RECORD_BYTES, oh = o + octant::HI_PIECE;
+                const bool fx = octant::far_first(r.inv.x), fy = octant::far_first(r.inv.y), fz_ = octant::far_first(r.inv.z);
+                const uint32_t nxo = fx ? oh : o, nyo = fy ? oh : o, nzo = fz_ ? oh : o;
+                const uint32_t fxo = fx ? o : oh, fyo = fy ? o : oh, fzo = fz_ ? o : oh;
+                xl = piece(nxo, 0u); yl = piece(nyo, 16u); zl = piece(nzo, 32u);
+                xh = piece(fxo, 0u); yh = piece(fyo, 16u); zh = piece(fzo, 32u);
+                lk = piece(o, 96u);
+                if (COUNT)
+                {
+                    count_vmem(cnt, qb + nxo, 1u, VMEM_QUAD); count_vmem(cnt, qb + nyo + 16u, 1u, VMEM_QUAD);
+                    count_vmem(cnt, qb + nzo + 32u, 1u, VMEM_QUAD); count_vmem(cnt, qb + fxo, 1u, VMEM_QUAD);
+                    count_vmem(cnt, qb + fyo + 16u, 1u, VMEM_QUAD); count_vmem(cnt, qb + fzo + 32u, 1u, VMEM_QUAD);
+                    count_vmem(cnt, qb + o + 96u, 1u, VMEM_QUAD);
+                }
+            }
+            else
+            {
+                const float4* p = quads + 8u * link;
+                xl = p[0]; yl = p[1]; zl = p[2]; xh = p[3]; yh = p[4]; zh = p[5]; lk = p[6];
+                if (COUNT) count_vmem(cnt, p, 7u, VMEM_QUAD);
+            }
             const uint32_t k0 = __float_as_uint(lk.x), k1 = __float_as_uint(lk.y);
             const uint32_t k2 = __float_as_uint(lk.z), k3 = __float_as_uint(lk.w);
             float d0, d1, d2, d3;
@@ -614,15 +646,30 @@ __device__ __forceinline__ int ray_step(const float4* __restrict__ pairs, const 
             }
             else
             {
-                // NEVER_HIT: the AO kernel's exact records hold a point box at +inf in every unused entry (vrh_quad.cpp,
-                // uploaded by the same build), which quad_entry fails for every finite ray -- tn = +inf, or tf = -inf
-                constexpr bool NEVER_HIT = QUAD_AO && NEVER_HIT_UNUSED;
-                h0 = quad_entry<FIN>(xl.x, yl.x, zl.x, xh.x, yh.x, zh.x, r, max_t, d0) & (NEVER_HIT || k0 != QUAD_NONE);
-                h1 = quad_entry<FIN>(xl.y, yl.y, zl.y, xh.y, yh.y, zh.y, r, max_t, d1) & (NEVER_HIT || k1 != QUAD_NONE);
-                h2 = quad_entry<FIN>(xl.z, yl.z, zl.z, xh.z, yh.z, zh.z, r, max_t, d2) & (NEVER_HIT || k2 != QUAD_NONE);
-                h3 = quad_entry<FIN>(xl.w, yl.w, zl.w, xh.w, yh.w, zh.w, r, max_t, d3) & (NEVER_HIT || k3 != QUAD_NONE);
+                if constexpr (OCT)
+                {
+                    // no link compare: the AO kernel's exact records hold a point box at +inf in every unused entry
+                    // (NEVER_HIT_UNUSED; vrh_quad.cpp, uploaded by the same build), which the test fails for every finite
+                    // ray -- tn = +inf, or tf = -inf
+                    static_assert(!OCT || NEVER_HIT_UNUSED, "the octant step compares no link");
+                    h0 = octant::entry<FIN>(xl.x, yl.x, zl.x, xh.x, yh.x, zh.x, r.ori.x, r.ori.y, r.ori.z, r.inv.x, r.inv.y, r.inv.z, max_t, d0);
+                    h1 = octant::entry<FIN>(xl.y, yl.y, zl.y, xh.y, yh.y, zh.y, r.ori.x, r.ori.y, r.ori.z, r.inv.x, r.inv.y, r.inv.z, max_t, d1);
+                    h2 = octant::entry<FIN>(xl.z, yl.z, zl.z, xh.z, yh.z, zh.z, r.ori.x, r.ori.y, r.ori.z, r.inv.x, r.inv.y, r.inv.z, max_t, d2);
+                    h3 = octant::entry<FIN>(xl.w, yl.w, zl.w, xh.w, yh.w, zh.w, r.ori.x, r.ori.y, r.ori.z, r.inv.x, r.inv.y, r.inv.z, max_t, d3);
+                }
+                else
+                {
+                    h0 = quad_entry<FIN>(xl.x, yl.x, zl.x, xh.x, yh.x, zh.x, r, max_t, d0) & (k0 != QUAD_NONE);
+                    h1 = quad_entry<FIN>(xl.y, yl.y, zl.y, xh.y, yh.y, zh.y, r, max_t, d1) & (k1 != QUAD_NONE);
+                    h2 = quad_entry<FIN>(xl.z, yl.z, zl.z, xh.z, yh.z, zh.z, r, max_t, d2) & (k2 != QUAD_NONE);
+                    h3 = quad_entry<FIN>(xl.w, yl.w, zl.w, xh.w, yh.w, zh.w, r, max_t, d3) & (k3 != QUAD_NONE);
+                }
             }
             if (COUNT) cnt.box += 4;
+            // the links are fetched with the planes, as the sorting step fetched them off its one address: left to the
+            // compiler, their load sinks below the exit of a record without a hit, and every record with one waits for it
+            // (measured 1.3 % slower).  The empty statement uses them here, at no instruction
+            if constexpr (OCT) asm volatile("" :: "v"(lk.x), "v"(lk.y), "v"(lk.z), "v"(lk.w));
             if (!(h0 | h1 | h2 | h3)) return st.empty() ? -1 : 0;
             auto push = [&](uint32_t v) { if constexpr (LDS_ONLY) st.push_lds(v); else st.push(v); };
             if (LDS_ONLY ? !st.template room_lds<COUNT>(3u) : !st.room(3u))

@@ -1,6 +1,6 @@
 """Identity of the kernel build a measurement belongs to: the SHA-256 of the sources libvrh's kernels
-are compiled from (visionaray_amd/csrc, include/vrh.h, include/visionaray_hip/detail/vrh_device.h and
-vrh_sampler.h, which holds the AO kernel's disk sample).
+are compiled from (visionaray_amd/csrc, include/vrh.h, include/visionaray_hip/detail/vrh_device.h,
+vrh_sampler.h, which holds the AO kernel's disk sample, and vrh_octant.h, its 4-wide entry test).
 tools/pmc_bench.py stores it in every committed PMC pass; bench.py reports the pass's counters only
 when the running tree has the same hash (a stale pass would report stale achieved / frac)."""
 import glob
@@ -16,7 +16,8 @@ def kernel_sources():
                    + glob.glob(os.path.join(_ROOT, "visionaray_amd", "csrc", "*.cpp")))
     return files + [os.path.join(_ROOT, "include", "vrh.h"),
                     os.path.join(_ROOT, "include", "visionaray_hip", "detail", "vrh_device.h"),
-                    os.path.join(_ROOT, "include", "visionaray_hip", "detail", "vrh_sampler.h")]
+                    os.path.join(_ROOT, "include", "visionaray_hip", "detail", "vrh_sampler.h"),
+                    os.path.join(_ROOT, "include", "visionaray_hip", "detail", "vrh_octant.h")]
 
 
 def _sha256(files):

@@ -19,6 +19,10 @@
 // QUAD_NONE for an unused entry.  An unused entry's box repeats entry 0's, or with `never_hit_unused` (the
 // default build's upload, vrh_device.h NEVER_HIT_UNUSED) is the point box lo = hi = +inf that no finite ray passes, so
 // the AO kernel's step needs no compare of the link; every other reader of the records keeps its link test.
+// That step also takes an axis' near plane from the sign of the ray's inverse direction instead of a min / max of
+// the two plane distances (vrh_octant.h), which is exact only for boxes with lo <= hi: build_quads refuses a tree in
+// which any node that becomes an entry has another box (valid_box; a NaN bound fails it), and a tree of 2^25 records
+// or more, whose byte offsets would not fit the step's 32 bits.
 #include "vrh_internal.h"
 #include "../../include/visionaray_hip/detail/vrh_fused_slab.h"
 
@@ -36,6 +40,11 @@ namespace vrh {
 
 namespace {
 
+// the AO kernel's octant step (vrh_octant.h) addresses a record by a 32-bit byte offset: 2^25 records of 128 B
+constexpr uint32_t MAX_RECORDS = 1u << 25;
+
+// lo <= hi on the three axes (a NaN bound fails).  The octant step relies on it for every used entry: it takes the
+// near plane of an axis from the sign of the ray's inverse direction, not from a min / max of the two distances
 bool valid_box(const node32& n)
 {
     for (int a = 0; a < 3; ++a)
@@ -125,7 +134,7 @@ bool build_quads(const node32* nodes, uint32_t num_nodes, std::vector<float>& ou
                     if (it == index.end())
                     {
                         gq = uint32_t(out.size() / 32);
-                        if (gq >= 0x7FFFFFFFu) return false;
+                        if (gq >= MAX_RECORDS) return false;
                         index[g] = gq;
                         out.resize(out.size() + 32, 0.0f);
                         queue.push_back({ g, depth + 1 });
