@@ -9,7 +9,7 @@ maker draws gp_sweep from the same generator (sweep_scene, sweep_shading, sweep_
 checks the sweep's coverage on the oracle's frames (CPU) and tests/test_gpu_fuzz_generic.py renders it (GPU).
 
 DEPTH_LIMIT: the deepest generic BVH each kernel's launch plan accepts at default options (the whole stack in
-LDS, no overflow block), as tests/cpp/launch_plan_generic_check.cpp prints them."""
+LDS, no overflow block), as tests/cpp/launch_plan_check.cpp limits prints them."""
 import ctypes as C
 import functools
 import json

@@ -169,7 +169,7 @@ DEEP_SPEC = dict(bg=(0.1, 0.2, 0.3, 1.0), ambient=(1.0, 1.0, 1.0, 1.0), ao_sampl
 
 @pytest.mark.parametrize("kind", G.KERNELS)
 def test_comb_at_the_lds_depth_limit_renders(ctx, oracle_mod, kind):
-    """the deepest tree the launch plan accepts for this kernel (tests/test_launch_plan_generic.py pins the number): the
+    """the deepest tree the launch plan accepts for this kernel (tests/test_launch_plan.py pins the number): the
     whole stack in LDS, all of a CU's 160 KiB in primary visibility and simple.  Against the oracle's frame and against
     the TRI64 upload of the same tree."""
     depth = G.DEPTH_LIMIT[kind]

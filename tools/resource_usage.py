@@ -3,7 +3,8 @@
 
     python tools/resource_usage.py [visionaray_amd/_lib/asm/resource-usage.txt] [filter]
 One line per render_unified_kernel instance: template arguments <KIND, AO, COUNT, OCC, EPI, LIST, BATCH,
-SPILL, SAMPLED, SHARE>, VGPRs, VGPR spills, scratch bytes per lane, SGPRs, SGPR spills, occupancy.
+SPILL, SAMPLED, SHARE, TEX, GEN> (the fields of vrh_launch.h's instance_key; TEX and GEN are its flavour),
+VGPRs, VGPR spills, scratch bytes per lane, SGPRs, SGPR spills, occupancy.
 """
 import re
 import subprocess

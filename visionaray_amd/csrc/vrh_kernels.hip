@@ -651,10 +651,10 @@ __device__ __forceinline__ uint32_t kernarg_stack_cap()
 // frames in flight) so that profiles tell them apart from one-frame launches (hip_sched::frame).
 // SPILL: the traversal stack may continue in the global overflow block (stack_t<true>).
 // TEX: the shading samples its diffuse maps at every surface it sets up (vrh_shading_set_textures; vrh_shade.h
-// surface_tex): EPI 1, 3, 4, 5.  The untextured instances are the same code as before the argument existed.
+// surface_tex): EPI 1, 3, 4, 5.
 // GEN: the scene holds generic primitives (VRH_PRIM_GENERIC80: triangles and spheres in one BVH; KIND is 0, the
-// leaf loop is KIND_GENERIC's): EPI 0 with and without AO, 1 and 3, the one-frame step loop, the whole stack in
-// LDS (vrh_launch.h generic_instance_exists).  Every other instance is the code it was before the argument existed.
+// leaf loop is KIND_GENERIC's): EPI 0 with and without AO, 1 and 3, the one-frame step loop, the whole stack in LDS.
+// (vrh_launch.h instance_exists says which combinations of the arguments are instantiated.)
 template <int KIND, bool AO, bool COUNT, int OCC, int EPI = 0, bool LIST = false, bool BATCH = false, bool SPILL = false,
           bool SAMPLED = false, bool SHARE = false, bool TEX = false, bool GEN = false>
 __global__ __launch_bounds__(256, OCC) void render_unified_kernel(render_params P)
@@ -1335,31 +1335,28 @@ __global__ void pack_code_kernel(const uint32_t* __restrict__ pid, const uint8_t
 using kernel_fn = void (*)(render_params);
 
 // the instance of key_at(I), named here and nowhere else: null where instance_exists says there is none
-// (TEX: the textured instance of the key, where textured_instance_exists says there is one;
-// GEN: the generic-primitive instance of the key, where generic_instance_exists says there is one)
-template <size_t I, bool TEX, bool GEN>
+// (the key's flavour gives the kernel's TEX and GEN arguments)
+template <size_t I>
 static kernel_fn instance_at()
 {
     constexpr instance_key k = key_at(I);
-    static_assert(!(TEX && GEN), "no textured generic-primitive instances");
-    if constexpr (GEN ? generic_instance_exists(k) : TEX ? textured_instance_exists(k) : instance_exists(k))
-        return dev::render_unified_kernel<k.kind, k.ao, k.count, k.occ, int(k.epi), k.list, k.batch, k.spill, k.sampled, k.share, TEX, GEN>;
+    if constexpr (instance_exists(k))
+        return dev::render_unified_kernel<k.kind, k.ao, k.count, k.occ, int(k.epi), k.list, k.batch, k.spill, k.sampled, k.share,
+                                          k.flavour == FLAVOUR_TEXTURED, k.flavour == FLAVOUR_GENERIC>;
     else
         return nullptr;
 }
 
-template <bool TEX, bool GEN, size_t... I>
+template <size_t... I>
 static kernel_fn find_instance(size_t i, std::index_sequence<I...>)
 {
-    static const kernel_fn table[NUM_KEYS + 1] = { instance_at<I, TEX, GEN>()..., nullptr };
+    static const kernel_fn table[NUM_KEYS + 1] = { instance_at<I>()..., nullptr };
     return table[i];
 }
 
 static kernel_fn select_variant(const launch_config& c)
 {
-    if (c.generic) return c.textured ? nullptr : find_instance<false, true>(key_index(c), std::make_index_sequence<NUM_KEYS>{});
-    return c.textured ? find_instance<true, false>(key_index(c), std::make_index_sequence<NUM_KEYS>{})
-                      : find_instance<false, false>(key_index(c), std::make_index_sequence<NUM_KEYS>{});
+    return find_instance(key_index(c), std::make_index_sequence<NUM_KEYS>{});
 }
 
 size_t render_lds_bytes(const launch_config& c)

@@ -1,6 +1,8 @@
 // visionaray_amd/csrc/vrh_launch.h -- the launch plan of vrh_render, host-only C++17 (no HIP header:
 // tests/cpp/launch_plan_check.cpp drives it with g++).  Three things live here:
-//   * instance_key / instance_exists: which render_unified_kernel instances exist.  vrh_kernels.hip
+//   * instance_key / instance_exists: which render_unified_kernel instances exist.  The key names every
+//     template argument of the kernel -- primitive kind, epilogue, launch form, flavour (plain, textured,
+//     generic primitives), ... -- so one key is one instance and key_index identifies it.  vrh_kernels.hip
 //     instantiates exactly the keys instance_exists accepts, and plan_launch produces exactly those;
 //   * tuning_options: the values of vrh_ctx_set_option the launch policy reads;
 //   * plan_launch: kernel description + scene info + options + one occupancy query -> the instance,
@@ -31,7 +33,16 @@ enum epilogue : int
 // register budget (waves / SIMD) of the path-tracing instances (render_unified_kernel<..., EPI 4 / 5>)
 constexpr int PATH_OCC = 5;
 
-// the ten template arguments of render_unified_kernel, by name
+// what the instance does beyond its key's other fields (render_unified_kernel's TEX and GEN arguments; one field,
+// not two flags: there is no textured generic-primitive instance)
+enum instance_flavour : int
+{
+    FLAVOUR_PLAIN = 0,
+    FLAVOUR_TEXTURED = 1,   // TEX: the shading samples its diffuse maps (vrh_shading_set_textures)
+    FLAVOUR_GENERIC = 2,    // GEN: the leaf loop walks generic primitives (VRH_PRIM_GENERIC80); kind stays 0
+};
+
+// the twelve template arguments of render_unified_kernel, by name (flavour stands for TEX and GEN)
 struct instance_key
 {
     int kind;          // 0 triangles, 1 spheres
@@ -44,13 +55,29 @@ struct instance_key
     bool spill;        // the traversal stack continues in a global overflow block
     bool sampled;      // a pixel-sampler pass (vrh_render_sampled): jittered / offset rays, blended colour
     bool share;        // AO tail sharing: one-frame AO launches at 5 waves / SIMD
+    instance_flavour flavour;
 };
 
-// The instance set, family by family.  Every register budget exists for the plain, frames-in-flight
-// and shading (simple / multi_hit / whitted) instances; every other family at the budgets the
-// defaults choose from.
+// The instance set.  The textured and the generic-primitive flavour narrow it first; what is left is decided
+// family by family: every register budget exists for the plain, frames-in-flight and shading (simple /
+// multi_hit / whitted) instances; every other family at the budgets the defaults choose from.
 constexpr bool instance_exists(const instance_key& k)
 {
+    if (k.flavour < FLAVOUR_PLAIN || k.flavour > FLAVOUR_GENERIC) return false;
+    // textured: the simple, whitted and path-tracing epilogues in the launch forms each has, without test
+    // counting, and uncapped (occ 1) only: capped at their families' 5 waves / SIMD the whitted and path-tracing
+    // ones spill 4-12 VGPRs (12-52 bytes of scratch per lane, -Rpass-analysis=kernel-resource-usage); uncapped
+    // they take 103-112 VGPRs (4 waves / SIMD) with no VGPR spill, so a textured launch runs at that lower budget
+    // whatever VRH_OPT_WAVES_PER_SIMD asks for
+    if (k.flavour == FLAVOUR_TEXTURED && (k.count || k.occ != 1 || k.epi == EPI_PLAIN || k.epi == EPI_MULTI_HIT)) return false;
+    // generic primitives: primary visibility, AO, simple and whitted on the one-frame step loop with the whole
+    // stack in LDS, uncounted, one register budget each -- primary 6 waves / SIMD, AO and whitted 5, simple
+    // uncapped (DESIGN.md section 3 has their resource usage)
+    if (k.flavour == FLAVOUR_GENERIC)
+    {
+        const int occ = k.epi == EPI_PLAIN ? (k.ao ? 5 : 6) : k.epi == EPI_SIMPLE ? 1 : k.epi == EPI_WHITTED ? 5 : 0;
+        if (k.kind != 0 || k.count || k.list || k.batch || k.sampled || k.spill || k.share || k.occ != occ) return false;
+    }
     if ((k.kind != 0 && k.kind != 1) || (k.occ != 1 && k.occ != 5 && k.occ != 6 && k.occ != 8)) return false;
     const bool step = !k.list && !k.batch && !k.sampled;           // the one-frame step loop
     if (int(k.list) + int(k.batch) + int(k.sampled) > 1) return false;
@@ -75,37 +102,13 @@ constexpr bool instance_exists(const instance_key& k)
     return !(k.batch && k.count);
 }
 
-// "Textured" is a second axis next to the key (render_unified_kernel's defaulted TEX argument): the
-// instances that sample the shading's diffuse maps (vrh_shading_set_textures).  They exist for the simple,
-// whitted and path-tracing epilogues in the launch forms each has -- one frame; the path tracer also
-// frames in flight and the pixel-sampler pass -- without test counting, and uncapped (occ 1) only: capped at
-// their families' 5 waves / SIMD the whitted and path-tracing ones spill 4-12 VGPRs (12-52 bytes of scratch
-// per lane, -Rpass-analysis=kernel-resource-usage); uncapped they take 103-112 VGPRs (4 waves / SIMD) with
-// no VGPR spill, so a textured launch runs at that lower budget whatever VRH_OPT_WAVES_PER_SIMD asks for.
-constexpr bool textured_instance_exists(const instance_key& k)
-{
-    if (!instance_exists(k) || k.count) return false;
-    return (k.epi == EPI_SIMPLE || k.epi == EPI_WHITTED || k.epi == EPI_PATH || k.epi == EPI_PATH_GENERIC) && k.occ == 1;
-}
-
-// "Generic" is a third axis of the same form (render_unified_kernel's defaulted GEN argument): the instances whose
-// leaf loop walks generic primitives (VRH_PRIM_GENERIC80, triangles and spheres in one BVH).  The key's kind stays
-// 0 -- the records are the triangle's three words -- so the key domain, and every instance outside this axis, is
-// what it was.  The set: primary visibility, AO, simple and whitted on the one-frame step loop with the whole
-// stack in LDS, uncounted, one register budget each -- primary 6 waves / SIMD, AO and whitted 5, simple uncapped
-// (DESIGN.md section 3 has their resource usage).
-constexpr bool generic_instance_exists(const instance_key& k)
-{
-    if (!instance_exists(k) || k.kind != 0 || k.count || k.list || k.batch || k.spill || k.sampled || k.share) return false;
-    if (k.epi == EPI_PLAIN) return k.occ == (k.ao ? 5 : 6);
-    if (k.epi == EPI_SIMPLE) return k.occ == 1;
-    if (k.epi == EPI_WHITTED) return k.occ == 5;
-    return false;
-}
-
-// the key domain as a mixed-radix index (vrh_kernels.hip builds its table of instances over it)
+// The key domain as a mixed-radix index (vrh_kernels.hip builds its table of instances over it).  The compiler
+// emits the kernels in the table's order, and the register allocation of some depends on their place in the code
+// object (profiles/launch_key/isa_identity.txt): the flavour is the most significant digit and runs generic
+// primitives, textured, plain, the order in which the recorded resource usage and profiles were taken
 constexpr int KEY_OCCS[4] = { 1, 5, 6, 8 };
-constexpr size_t NUM_KEYS = 2 * 2 * 2 * 4 * 6 * 32;
+constexpr size_t KEYS_PER_FLAVOUR = 2 * 2 * 2 * 4 * 6 * 32;
+constexpr size_t NUM_KEYS = KEYS_PER_FLAVOUR * 3;
 constexpr instance_key key_at(size_t i)
 {
     instance_key k{};
@@ -114,25 +117,37 @@ constexpr instance_key key_at(size_t i)
     k.count = i % 2 != 0; i /= 2;
     k.occ = KEY_OCCS[i % 4]; i /= 4;
     k.epi = epilogue(i % 6); i /= 6;
-    k.list = (i & 1) != 0; k.batch = (i & 2) != 0; k.spill = (i & 4) != 0; k.sampled = (i & 8) != 0; k.share = (i & 16) != 0;
+    k.list = (i & 1) != 0; k.batch = (i & 2) != 0; k.spill = (i & 4) != 0; k.sampled = (i & 8) != 0; k.share = (i & 16) != 0; i /= 32;
+    k.flavour = instance_flavour(FLAVOUR_GENERIC - int(i));
     return k;
 }
 // NUM_KEYS for a key outside the domain (no instance)
 constexpr size_t key_index(const instance_key& k)
 {
     const size_t o = k.occ == 1 ? 0 : k.occ == 5 ? 1 : k.occ == 6 ? 2 : k.occ == 8 ? 3 : 4;
-    if ((k.kind != 0 && k.kind != 1) || o == 4 || k.epi < EPI_PLAIN || k.epi > EPI_PATH_GENERIC) return NUM_KEYS;
+    if ((k.kind != 0 && k.kind != 1) || o == 4 || k.epi < EPI_PLAIN || k.epi > EPI_PATH_GENERIC || k.flavour < FLAVOUR_PLAIN
+        || k.flavour > FLAVOUR_GENERIC)
+        return NUM_KEYS;
     const size_t flags = size_t(k.list) | size_t(k.batch) << 1 | size_t(k.spill) << 2 | size_t(k.sampled) << 3 | size_t(k.share) << 4;
-    return size_t(k.kind) + 2 * (size_t(k.ao) + 2 * (size_t(k.count) + 2 * (o + 4 * (size_t(k.epi) + 6 * flags))));
+    return size_t(k.kind) + 2 * (size_t(k.ao) + 2 * (size_t(k.count) + 2 * (o + 4 * (size_t(k.epi) + 6 * (flags
+           + 32 * size_t(FLAVOUR_GENERIC - k.flavour))))));
 }
+
+// the size of the instance set, flavour by flavour, beside the rule that makes it
+constexpr size_t num_instances(instance_flavour f)
+{
+    size_t n = 0;
+    for (size_t i = 0; i < KEYS_PER_FLAVOUR; ++i) n += instance_exists(key_at(size_t(FLAVOUR_GENERIC - f) * KEYS_PER_FLAVOUR + i)) ? 1 : 0;
+    return n;
+}
+static_assert(num_instances(FLAVOUR_PLAIN) == 114 && num_instances(FLAVOUR_TEXTURED) == 8 && num_instances(FLAVOUR_GENERIC) == 4,
+              "the render_unified_kernel instances: 114 plain, 8 textured, 4 generic-primitive");
 
 struct launch_config : instance_key
 {
     int block;         // threads per block (multiple of 64)
     int stack_cap;     // LDS stack entries per lane
     int max_hits;      // MULTI_HIT: N (LDS hit lists)
-    bool textured;     // the TEX instance of the key (textured_instance_exists)
-    bool generic = false;   // the GEN instance of the key (generic_instance_exists)
 };
 
 // dynamic LDS of a launch; `ao_wave_words` (the per-wave AO area) and `whitted_lane_words` (the
@@ -163,12 +178,12 @@ struct launch_inputs
     bool textured = false;                  // the shading has textures attached (vrh_shading_set_textures)
     uint32_t num_frames = 1;
     // the scene: vrh_scene_info and what the upload found (root_is_pair0: roots[0] == 0)
+    // (prim_kind VRH_PRIM_GENERIC80: generic primitives, triangles and spheres in one BVH)
     uint32_t prim_kind = VRH_PRIM_TRI64, max_depth = 1, num_roots = 1;
     uint64_t device_bytes = 0;
     bool finite_bounds = true, has_quads = false, root_is_pair0 = true;
     bool radius_finite = true;              // AO: the radius is <= FLT_MAX (the 4-wide step's test relies on it)
     tuning_options opt;
-    bool generic = false;                   // the scene holds generic primitives (VRH_PRIM_GENERIC80)
 };
 
 // the two questions the plan asks the device side
@@ -193,7 +208,7 @@ struct launch_plan
 };
 
 // the register budget nearest to `want` at which the family of `k` has an instance: the largest one
-// not above it, else the smallest (a family with every budget keeps `want`)
+// not above it, else the smallest (a family with every budget keeps `want`; 0: it has none)
 constexpr int family_occ(instance_key k, int want)
 {
     int below = 0, least = 0;
@@ -206,36 +221,9 @@ constexpr int family_occ(instance_key k, int want)
     }
     return below ? below : least;
 }
-// the same among the textured instances of the family of `k` (0: it has none)
-constexpr int textured_family_occ(instance_key k, int want)
-{
-    int below = 0, least = 0;
-    for (int i = 3; i >= 0; --i)
-    {
-        k.occ = KEY_OCCS[i];
-        if (!textured_instance_exists(k)) continue;
-        least = k.occ;
-        if (below == 0 && k.occ <= want) below = k.occ;
-    }
-    return below ? below : least;
-}
 
-// the same among the generic-primitive instances
-constexpr int generic_family_occ(instance_key k, int want)
-{
-    int below = 0, least = 0;
-    for (int i = 3; i >= 0; --i)
-    {
-        k.occ = KEY_OCCS[i];
-        if (!generic_instance_exists(k)) continue;
-        least = k.occ;
-        if (below == 0 && k.occ <= want) below = k.occ;
-    }
-    return below ? below : least;
-}
-
-// A generic-primitive scene: what the launch asks for beyond the GEN instances is refused here, by name, before
-// anything is planned ("" where nothing is).
+// A generic-primitive scene: what the launch asks for beyond the instances of that flavour is refused here, by name,
+// before anything is planned ("" where nothing is).
 inline std::string generic_refusal(const launch_inputs& in)
 {
     const char* what = in.num_roots > 1 ? "BVH lists"
@@ -255,7 +243,8 @@ inline std::string generic_refusal(const launch_inputs& in)
 
 inline int plan_launch(const launch_inputs& in, const launch_device& dev, launch_plan& out, std::string& err)
 {
-    if (in.generic)
+    const bool generic = in.prim_kind == VRH_PRIM_GENERIC80;
+    if (generic)
     {
         err = generic_refusal(in);
         if (!err.empty()) return VRH_ERR_UNSUPPORTED;
@@ -275,8 +264,9 @@ inline int plan_launch(const launch_inputs& in, const launch_device& dev, launch
     const uint32_t cap = opt.stack ? uint32_t(opt.stack) : total;
     if (cap < 1u) { err = "vrh_render: stack capacity option must be >= 1"; return VRH_ERR_INVALID; }
     launch_config lc{};
-    lc.kind = (in.generic || in.prim_kind == VRH_PRIM_TRI64) ? 0 : 1;
-    lc.generic = in.generic;
+    lc.kind = (generic || in.prim_kind == VRH_PRIM_TRI64) ? 0 : 1;
+    // (generic_refusal has turned a textured shading over generic primitives away)
+    lc.flavour = generic ? FLAVOUR_GENERIC : in.textured ? FLAVOUR_TEXTURED : FLAVOUR_PLAIN;
     lc.ao = ao;
     lc.count = in.count_tests;
     lc.stack_cap = int(cap);
@@ -319,31 +309,23 @@ inline int plan_launch(const launch_inputs& in, const launch_device& dev, launch
     const int occ_ao = (opt.share == 1 || lc.count) ? 5 : 6;
     const int occ_primary = (!lc.count && (lc.kind == 0 || num_frames > 1)) ? 8 : 6;
     const int occ_default = path ? PATH_OCC : whitted ? 5 : lc.epi ? 1 : lc.ao ? occ_ao : occ_primary;
-    // sampler passes, BVH lists and the path tracer have instances at some budgets only: the nearest one
+    // sampler passes, BVH lists, the path tracer and the textured and generic-primitive flavours have instances
+    // at some budgets only: the nearest one
     lc.occ = family_occ(lc, opt.occ ? opt.occ : occ_default);
-    if (in.textured)
+    // a flavour has instances for part of what vrh_render's argument validation lets through
+    // (of the plain one, all of it: tests/cpp/launch_plan_check.cpp)
+    if (lc.flavour != FLAVOUR_PLAIN && !instance_exists(lc))
     {
-        // a textured shading runs the TEX instance of its key: at the nearest register budget that has one
-        lc.textured = true;
-        lc.occ = textured_family_occ(lc, opt.occ ? opt.occ : occ_default);
-        if (!textured_instance_exists(lc))
-        {
-            err = multi ? "vrh_render: multi_hit takes no textures"
-                : lc.count ? "vrh_render: a textured shading has no test-counting instance"
-                           : "vrh_render: no textured instance of this kernel";
-            return VRH_ERR_UNSUPPORTED;
-        }
-    }
-    if (in.generic)
-    {
-        // a generic-primitive scene runs the GEN instance of its key, at the one register budget it has
-        lc.occ = generic_family_occ(lc, opt.occ ? opt.occ : occ_default);
-        if (!generic_instance_exists(lc)) { err = "vrh_render: no generic-primitive instance of this kernel"; return VRH_ERR_UNSUPPORTED; }
+        err = generic ? "vrh_render: no generic-primitive instance of this kernel"
+            : multi ? "vrh_render: multi_hit takes no textures"
+            : lc.count ? "vrh_render: a textured shading has no test-counting instance"
+                       : "vrh_render: no textured instance of this kernel";
+        return VRH_ERR_UNSUPPORTED;
     }
     // AO tail sharing needs several waves per block (they share LDS): 4 unless the block is set.
     // It has instances for uncounted one-frame AO launches at 5 waves / SIMD only: where there is no
-    // SHARE instance the option changes nothing, not even the block size (a generic-primitive scene has none)
-    lc.share = opt.share == 1 && !in.generic;
+    // SHARE instance the option changes nothing, not even the block size
+    lc.share = opt.share == 1;
     lc.share = lc.share && instance_exists(lc);
     lc.block = opt.block ? opt.block : lc.share ? 256 : 64;
     // auto: the LDS part of the stack shrinks (in steps of 4 entries) while LDS, not registers,
@@ -352,7 +334,7 @@ inline int plan_launch(const launch_inputs& in, const launch_device& dev, launch
     // (the primary / AO step loops at their default register budgets have overflow-stack instances;
     // every other kernel keeps its whole stack in LDS, as does an explicit VRH_OPT_STACK_CAP >= depth)
     lc.spill = true;
-    lc.spill = !in.generic && instance_exists(lc) && (!opt.stack || cap < total);
+    lc.spill = instance_exists(lc) && (!opt.stack || cap < total);
     if (lc.spill && !opt.stack)
     {
         launch_config lo = lc;

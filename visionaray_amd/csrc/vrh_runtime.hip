@@ -1260,7 +1260,6 @@ int plan_render(const vrh_ctx* ctx, const vrh_scene* sc, uint32_t num_frames, co
     in.generic_shading = k->shading && k->shading->gmaterials;
     in.textured = k->shading && k->shading->num_textures != 0 && k->kind != VRH_KERNEL_PRIMARY && k->kind != VRH_KERNEL_AO;
     in.sampler_pass = sampler_pass; in.hit_mask = k->hit_mask != nullptr; in.num_frames = num_frames;
-    in.generic = sc->info.prim_kind == VRH_PRIM_GENERIC80;
     in.prim_kind = sc->info.prim_kind; in.max_depth = sc->info.max_depth; in.num_roots = sc->num_roots;
     in.device_bytes = sc->info.device_bytes;
     in.finite_bounds = sc->finite_bounds; in.has_quads = sc->quads != nullptr; in.root_is_pair0 = sc->roots[0] == 0u;
